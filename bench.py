@@ -10,15 +10,20 @@ fixed synthetic batch resident in HBM.  With N>1 every rank runs i
 (weak scaling) and the fp32 gradient arena is averaged with RCCL all-reduce buckets launched from inside
 the backward pass.  Rank 0 prints ONE JSON line.
 
-Extra objects on the line:
+A plain run sets up, warms up, times the K steps and prints the line; beside the headline keys it carries
   roofline     — the dominant kernel of the step (by measured time), bracketed by HIP events on the
                  launch stream during the timed region (every launch of it in every 4th timed step,
                  --bracket-every); achieved = algorithmic FLOPs (or bytes) of those launches / their
                  summed duration.
+--full adds everything that takes runs of its own, among them:
+  roofline_hbm / roofline_more — the other priced entry points, bracketed in an untimed second pass.
   cpu_baseline — the oracle's torch-CPU port of the reference (oracle/net_ref.py), same synthetic
                  distribution, bounded sample, timed on this host's cores (rank 0, N=1 only).
   nms          — BASELINE config 5: 100k boxes x 20 classes per-class NMS, GPU boxes/s and the
                  single-thread C restatement of torchvision's CPU kernel beside it.
+  config0 / config3 / map / prep / optimizer / pcie_inclusive / dp_overhead — the side legs (N=1);
+  data_parallel — RCCL evidence and measured all-reduce times (N>1).
+--dump-outputs DIR writes what the last timed step handed its caller as DIR/<name>.npy (dump_outputs).
 """
 import argparse
 import json
@@ -146,6 +151,10 @@ def parse():
     ap.add_argument("--full-json", action="store_true", help="print the verbose line (explanatory strings, plan fingerprints, algorithmic bytes per "
                     "entry point: what tools/prof_*summary.py read) instead of the compact one sized for an 8 kB stdout tail")
     ap.add_argument("--detail", default="", help="comma list of entry points (or `all`): print their per-call table to stderr")
+    ap.add_argument("--full", action="store_true", help="also run what the headline does not need: the untimed second roofline pass, the CPU "
+                    "baselines, the side legs (configs[0] / [3], NMS, mAP, prep, optimizer, PCIe, 1-rank RCCL) and the N>1 RCCL evidence")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed (both loss tuples, every parameter gradient) as DIR/<name>.npy")
     return ap.parse_args()
 
 
@@ -857,6 +866,36 @@ def measure_allreduce(plan, reducer, world, reps=15):
             "note": "isolated (nothing overlapping), blocking collectives on a copy of the arena; inside a step all but the last bucket ride under backward"}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, out, model):
+    """--dump-outputs DIR: what the timed path handed its caller in the LAST timed step, as float32 DIR/<name>.npy — both heads'
+    (loss, 6 metrics) tuples (head<i>_loss_metrics) and every parameter gradient backward left (grad.<parameter name>).  The inputs
+    are seeded (torch.manual_seed(0) init, synthetic batch of seed rank), so two builds run with the same arguments compare array for
+    array.  Should the arrays exceed 64 MB in all, each is cut to a fixed, seeded sample of its elements (same indices every run)."""
+    import numpy as np
+    arrays = {}
+    for i, r in enumerate(out):
+        arrays["head%d_loss_metrics" % i] = np.array([float(v.detach()) if torch.is_tensor(v) else float(v) for v in r], dtype=np.float32)
+    for k, p in model.named_parameters():
+        if p.grad is not None:
+            arrays["grad." + k] = p.grad.detach().float().cpu().numpy()
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        frac = (DUMP_LIMIT_BYTES - 4 * len(arrays)) / total
+        rng = np.random.RandomState(0)
+        for k in sorted(arrays):
+            v = arrays[k].reshape(-1)
+            n = max(1, int(v.size * frac))
+            if n < v.size:
+                arrays[k] = v[np.sort(rng.choice(v.size, n, replace=False))]
+    os.makedirs(path, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), v)
+    return len(arrays), sum(v.nbytes for v in arrays.values())
+
+
 def main():
     a = parse()
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -915,7 +954,7 @@ def main():
         out = step()
     torch.cuda.synchronize()
     plan = model._plans[(a.batch, a.size, a.size, True) + (("bf16",) if a.dtype == "bf16" else ())]
-    dp_info = dp_evidence_after_warmup(plan, reducer, out, world, rank, device) if use_dp else None
+    dp_info = dp_evidence_after_warmup(plan, reducer, out, world, rank, device) if use_dp and a.full else None
 
     # timed region: K steps, barrier + sync on both sides; the dominant kernels are bracketed by HIP events
     inline = a.roofline_pass == "inline" or a.breakdown
@@ -944,6 +983,9 @@ def main():
     if world > 1:
         dist.barrier()
     dt = time.perf_counter() - t0
+    if a.dump_outputs and rank == 0:             # before anything below runs the step again
+        n_arr, n_bytes = dump_outputs(a.dump_outputs, out, model)
+        print("bench: wrote %d arrays (%.1f MB) to %s" % (n_arr, n_bytes / 1e6, a.dump_outputs), file=sys.stderr)
     if not inline:                               # roofline leg: the same K steps again, MFMA kernels bracketed by HIP events
         plan.enable_timing(only=MFMA_KERNELS, steps=a.steps)
         for _ in range(a.steps):
@@ -968,7 +1010,7 @@ def main():
                     k = (which, idx)
                     per.setdefault(k, [name, calls[idx][3] or {}, 0.0])[2] += e0.elapsed_time(e1)
     second = None
-    if world == 1 and not a.breakdown:                # untimed second pass (single GPU only): the other priced entry points, bracketed
+    if world == 1 and not a.breakdown and a.full:     # untimed second pass (single GPU only): the other priced entry points, bracketed
         k2 = max(3, min(a.steps, 10))
         plan.enable_timing(only=set(SECOND_PASS), steps=k2)
         for _ in range(k2):
@@ -983,7 +1025,7 @@ def main():
         t = torch.tensor([dt], device=device, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
-    if use_dp:
+    if dp_info is not None:
         try:
             dp_info["allreduce_measured"] = measure_allreduce(plan, reducer, world)
         except Exception as e:                                                  # noqa: BLE001 — evidence, never the headline
@@ -1070,12 +1112,12 @@ def main():
             res["roofline_hbm"] = hb[0]               # the bandwidth-bound depthwise forward (north-star target: frac >= 0.6)
         if others:
             res["roofline_more"] = [o for o in others if not o["kernel"].startswith("mny_dw_fwd")]   # wgrad, dgrad+reduce (MFMA) and the fused expand-unit backward (HBM)
-        if world == 1 and not a.no_cpu_baseline:
+        if world == 1 and a.full and not a.no_cpu_baseline:
             try:
                 res["cpu_baseline"] = cpu_baseline()
             except Exception as e:                                              # noqa: BLE001 — reported, never at the cost of the line
                 res["cpu_baseline"] = {"error": repr(e)[:300]}
-        if world == 1 and not a.no_nms and headline and not use_dp:
+        if world == 1 and a.full and not a.no_nms and headline and not use_dp:
             try:
                 res["dp_overhead"] = dp_overhead_leg(a)
                 res["dp_overhead"]["timed_region_ms_per_step"] = round(dt / a.steps * 1e3, 3)
@@ -1113,7 +1155,7 @@ def main():
                 signal.alarm(0)
                 signal.signal(signal.SIGALRM, old)
         try:
-            if world == 1 and not a.no_nms and headline:
+            if world == 1 and a.full and not a.no_nms and headline:
                 del out
                 side("config3", with_budget, 240, config3_leg, device)
                 if not a.no_cpu_baseline and isinstance(res.get("config3"), dict) and "error" not in res["config3"]:
@@ -1122,7 +1164,7 @@ def main():
                     except Exception as e:                                      # noqa: BLE001
                         res["config3"]["cpu_baseline"] = {"error": repr(e)[:200]}
                 side("config0", with_budget, 120, c1_leg, device)
-            if world == 1 and not a.no_nms:
+            if world == 1 and a.full and not a.no_nms:
                 side("nms", nms_bench, device)
                 side("map", map_bench, device)
                 side("prep", prep_bench, device)

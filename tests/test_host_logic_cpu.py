@@ -135,3 +135,42 @@ def test_compact_bench_line_fits_an_8k_tail_and_keeps_every_roofline_object():
     assert fr == sorted(fr)                                                             # worst first
     tail = line[-5000:]                                                                 # even a 5 kB tail holds the roofline block and configs[3]
     assert '"roofline_more"' in tail and '"config3"' in tail and '"roofline_hbm"' in tail
+
+
+def test_bench_side_legs_are_opt_in_and_dump_outputs_is_seeded_float_and_capped(tmp_path, monkeypatch):
+    """A plain `bench.py` run does only what the headline needs: everything else sits behind --full (off by default).
+    --dump-outputs DIR writes both loss tuples and every parameter gradient as float32 .npy files, identical for identical
+    inputs, and a fixed seeded sample of every array once the whole dump would exceed its cap."""
+    import importlib.util
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_mod4", os.path.join(repo, "bench.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    monkeypatch.setattr("sys.argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    a = b.parse()
+    assert a.full is False and a.dump_outputs is None and a.steps == 3
+    monkeypatch.setattr("sys.argv", ["bench.py", "--full", "--dump-outputs", str(tmp_path / "x")])
+    a = b.parse()
+    assert a.full is True and a.dump_outputs == str(tmp_path / "x")
+    torch.manual_seed(0)
+    m = torch.nn.Sequential(torch.nn.Linear(64, 32), torch.nn.Linear(32, 3, bias=False))
+    m[1].weight.requires_grad_(False)                     # no gradient -> no file
+    m(torch.randn(5, 64)).sum().backward()
+    out = tuple(tuple(torch.tensor(0.5 * i + j) for j in range(7)) for i in range(2))
+    names = sorted(["head0_loss_metrics.npy", "head1_loss_metrics.npy", "grad.0.weight.npy", "grad.0.bias.npy"])
+    full_bytes = 4 * (14 + 64 * 32 + 32)
+    assert b.dump_outputs(str(tmp_path / "a"), out, m) == (4, full_bytes)
+    assert sorted(os.listdir(tmp_path / "a")) == names
+    z = {n: np.load(str(tmp_path / "a" / n)) for n in names}
+    assert all(v.dtype == np.float32 for v in z.values())
+    assert z["head1_loss_metrics.npy"].tolist() == [0.5 + j for j in range(7)]
+    np.testing.assert_array_equal(z["grad.0.weight.npy"], m[0].weight.grad.numpy())
+    monkeypatch.setattr(b, "DUMP_LIMIT_BYTES", 4096)
+    n1 = b.dump_outputs(str(tmp_path / "c1"), out, m)
+    n2 = b.dump_outputs(str(tmp_path / "c2"), out, m)
+    assert n1 == n2 and n1[1] <= 4096
+    for n in names:
+        c1, c2 = np.load(str(tmp_path / "c1" / n)), np.load(str(tmp_path / "c2" / n))
+        assert c1.dtype == np.float32 and np.array_equal(c1, c2)
+    w = np.load(str(tmp_path / "c1" / "grad.0.weight.npy"))
+    assert 0 < w.size < 64 * 32 and np.isin(w, m[0].weight.grad.numpy().reshape(-1)).all()

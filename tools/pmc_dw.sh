@@ -1,16 +1,18 @@
-# FETCH_SIZE / WRITE_SIZE of the depthwise forward variants (separate --pmc passes, program directly after `--`)
+# FETCH_SIZE / WRITE_SIZE of the depthwise forward variants (separate --pmc passes over bench.py --full, program directly after `--`)
 R=$GRAFT_REPO_ROOT
+OUT=${OUT:-$R/prof_out}      # where the runs write (git-ignored)
+mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 run() {  # tag, counter
-  rocprofv3 --pmc $2 --output-format csv -d $R/gpurun_out/pmc_$1_$2 -o run -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-nms > /dev/null 2> $R/gpurun_out/pmc_$1_$2.err
+  rocprofv3 --pmc $2 --output-format csv -d $OUT/pmc_$1_$2 -o run -- python3 $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-nms > /dev/null 2> $OUT/pmc_$1_$2.err
 }
 run A FETCH_SIZE; run A WRITE_SIZE
 export MNY_DW_XCD=0; run B FETCH_SIZE; unset MNY_DW_XCD
 export MNY_DW_V1=1; run D FETCH_SIZE; run D WRITE_SIZE; unset MNY_DW_V1
-cd $R
+cd $OUT
 python3 - <<'PY'
 import csv, glob, collections, os, re
-for d in sorted(glob.glob('gpurun_out/pmc_*_*_SIZE')):
+for d in sorted(glob.glob('pmc_*_*_SIZE')):
     f = glob.glob(d + '/**/run_counter_collection.csv', recursive=True)
     if not f: print(d, 'no csv'); continue
     tot = collections.defaultdict(float); cnt = collections.Counter()

@@ -1,13 +1,16 @@
-# HBM read traffic of the weight-gradient kernels with and without the XCD-aware block order (rocprofv3 --pmc FETCH_SIZE, own runs)
+# HBM read traffic of the weight-gradient kernels with and without the XCD-aware block order (rocprofv3 --pmc FETCH_SIZE, own runs;
+# bench.py --full: 1 warm-up + 2 timed + 3 second-pass = 6 steps)
 set -e
 REPO=$GRAFT_REPO_ROOT
+export OUT=${OUT:-$REPO/prof_out}      # where the runs write (git-ignored)
+mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --pmc FETCH_SIZE --output-format csv -d $REPO/gpurun_out/pmc_wg_xcd -o run -- python3 $REPO/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-nms > /dev/null 2> $REPO/gpurun_out/pmc_wg_xcd.err
+rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_wg_xcd -o run -- python3 $REPO/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-nms > /dev/null 2> $OUT/pmc_wg_xcd.err
 export MNY_WGRAD_NO_XCD=1
-rocprofv3 --pmc FETCH_SIZE --output-format csv -d $REPO/gpurun_out/pmc_wg_plain -o run -- python3 $REPO/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-nms > /dev/null 2> $REPO/gpurun_out/pmc_wg_plain.err
+rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_wg_plain -o run -- python3 $REPO/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-nms > /dev/null 2> $OUT/pmc_wg_plain.err
 python3 - <<'PY'
 import csv, glob, os, collections
-R = os.environ["GRAFT_REPO_ROOT"] + "/gpurun_out/"
+R = os.environ["OUT"] + "/"
 for tag in ("pmc_wg_xcd", "pmc_wg_plain"):
     f = glob.glob(R + tag + "/**/*counter_collection.csv", recursive=True)[0]
     tot = collections.Counter()
