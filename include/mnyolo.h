@@ -487,6 +487,65 @@ size_t mny_prep_ws_bytes(int N, int max_in_h, int max_in_w, int out_h, int out_w
 int mny_prep_batch(const uint8_t* src, const mny_image_desc* desc, int N, int max_in_h, int max_in_w, int out_h,
                    int out_w, const float* mean3, const float* std3, float* out, void* ws, void* stream);
 
+/* ---- device-side training augmentation (csrc/augment.hip) ------------------------------------------------------
+ * The train-phase sample path of the reference's data pipeline, after decoding: per image transform_od
+ * (image_augmentation.py:279-334: photometric_distort -> expand_od -> random_crop_od -> flip_od), for groups of
+ * 2..4 images Mosaic (:216-278) on a square canvas, then collate_fn's BILINEAR resize + ToTensor + Normalize
+ * (folder2lmdb.py:223-256).  Every draw is made on the host (augment.py TrainAugment.plan); the device only does
+ * the pixel work, bit for bit against Pillow:
+ *   photometric ops at source resolution, uint8 -> uint8 (Image.blend with a float alpha for brightness /
+ *   contrast / saturation, contrast's grey = int(mean(L) + 0.5) of the image as it is at that point of the chain,
+ *   Pillow RGB<->HSV for hue, a host-built 256-entry map for gamma); the geometry is read THROUGH (expand canvas
+ *   with filler 127, crop window, horizontal flip) by the resample, nothing is materialised for a single image;
+ *   Mosaic tiles are Pillow BICUBIC resizes (a = -0.5) pasted into a uint8 canvas whose mask rectangle is filled
+ *   with trunc(sum / count) of the resized tile per channel; the final resize is Pillow BILINEAR, then
+ *   out = (u8/255 - mean)/std in fp32.
+ * mny_aug_item (DEVICE array, one per decoded image): src = byte offset (a multiple of 4) + size of the image in
+ *   `src`; op[0..n_ops) in application order (MNY_AUG_*), factor[k] = the blend alpha of op k; hue_shift = the
+ *   uint8 added to H; gamma_map = the point() table; expand: the canvas size and the image's place in it (exp_h =
+ *   h, exp_w = w, exp_top = exp_left = 0 when not expanded); crop: the window inside the expanded image (all of it
+ *   when not cropped); flip; sample = the output index; mosaic members also carry their tile rectangle (top-left +
+ *   size of the resized image in the canvas) and mask rectangle (x0, y0, x1, y1).
+ * mny_aug_sample (DEVICE array, one per output image): items [first_item, first_item + n_items); n_items 1 = a
+ *   single image, 2..4 = a mosaic drawn on canvas slot `canvas_slot` (0..n_mosaic-1).
+ * max_in_h/max_in_w bound every source image AND every expanded / cropped image; canvas = the mosaic side.  An
+ * item outside the bounds (or a misaligned offset, an op list longer than 5, a tile outside its mask) is not read,
+ * its sample is written as zeros and the int32 at ws+0 receives 1 + its index; a malformed sample record
+ * receives -(1 + sample index).  mean3/std3: HOST arrays of 3 floats.  out: [n_out,3,out_h,out_w] fp32.
+ * ws: mny_aug_ws_bytes() (same arguments).  No host sync, no allocation; deterministic launch to launch.
+ * mny_aug_photometric: the photometric chain alone, item k writes dst + items[k].src.offset (dst laid out like
+ * src); only src, the op fields and the bounds are read; ws: at least mny_aug_ws_bytes(n, 0, 0, max_in_h,
+ * max_in_w, 0, 1, 1) bytes. */
+#define MNY_AUG_BRIGHTNESS 0
+#define MNY_AUG_CONTRAST 1
+#define MNY_AUG_SATURATION 2
+#define MNY_AUG_HUE 3
+#define MNY_AUG_GAMMA 4
+typedef struct mny_aug_item {
+    mny_image_desc src;
+    int32_t n_ops;
+    int32_t op[5];
+    float factor[5];
+    int32_t hue_shift;
+    uint8_t gamma_map[256];
+    int32_t exp_h, exp_w, exp_top, exp_left;
+    int32_t crop_top, crop_left, crop_h, crop_w;
+    int32_t flip;
+    int32_t sample;
+    int32_t tile_x, tile_y, tile_w, tile_h;
+    int32_t mask_x0, mask_y0, mask_x1, mask_y1;
+} mny_aug_item; /* 392 bytes */
+typedef struct mny_aug_sample {
+    int32_t first_item, n_items, canvas_slot, reserved;
+} mny_aug_sample;
+size_t mny_aug_ws_bytes(int n_items, int n_out, int n_mosaic, int max_in_h, int max_in_w, int canvas, int out_h,
+                        int out_w);
+int mny_aug_photometric(const uint8_t* src, const mny_aug_item* items, int n, int max_in_h, int max_in_w,
+                        uint8_t* dst, void* ws, void* stream);
+int mny_aug_batch(const uint8_t* src, const mny_aug_item* items, int n_items, const mny_aug_sample* samples,
+                  int n_out, int max_in_h, int max_in_w, int canvas, int n_mosaic, int out_h, int out_w,
+                  const float* mean3, const float* std3, float* out, void* ws, void* stream);
+
 /* ---- bf16 STORAGE twins (BASELINE config 4: MobileNetV3-YOLO 512x512 bf16) -----------------
  * Every `mny_X_bf16` has the contract of `mny_X` above with ONE difference: the activation-sized tensors (the
  * `void*` parameters: raw conv outputs, materialised sums, gradients wrt activations) are bf16 in HBM.  Kernels

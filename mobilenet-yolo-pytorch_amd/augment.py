@@ -1,0 +1,280 @@
+"""Device-side training augmentation — the train-phase sample path of the reference's data pipeline after decoding:
+per image `transform_od` (utils/image_augmentation.py:279-334: photometric_distort, expand_od, random_crop_od, flip_od),
+for groups of 2-4 images `Mosaic` (:216-278), then `collate_fn`'s resize + normalise (folder2lmdb.py:223-265).
+
+`TrainAugment.plan` makes every random draw on the host, consuming the RNG in exactly the reference's order (per
+group, per member: photometric -> expand gate -> expand -> crop loop -> flip; then the mosaic draws; the batch's size
+choice last), and does the box maths with the same torch CPU fp32 ops, so targets are bit-equal.  `__call__` packs the
+decoded uint8 images into one pinned upload and runs `mny_aug_batch` (csrc/augment.hip): photometric chain, geometry,
+mosaic canvas and the final BILINEAR resize + Normalize, bit for bit against Pillow.
+
+Not covered (stays with the caller): imgaug's `seq` (folder2lmdb.py:28-42, applied to the decoded image before this
+stage, which is the reference's order too), JPEG decoding, the sampler, and seg maps (a config with a `seg:` section
+is refused).  No CPU fallback: without libmnyolo.so every call raises MnyError."""
+import ctypes
+import math
+import random
+
+import numpy as np
+import torch
+
+from ._lib import call, query
+from .prep import BatchPrep
+
+BRIGHTNESS, CONTRAST, SATURATION, HUE, GAMMA = range(5)      # MNY_AUG_*; image_augmentation.py:178-182 order
+
+ITEM = np.dtype([("offset", np.int64), ("h", np.int32), ("w", np.int32), ("n_ops", np.int32), ("op", np.int32, 5),
+                 ("factor", np.float32, 5), ("hue_shift", np.int32), ("gamma_map", np.uint8, 256),
+                 ("exp", np.int32, 4), ("crop", np.int32, 4), ("flip", np.int32), ("sample", np.int32),
+                 ("tile", np.int32, 4), ("mask", np.int32, 4)], align=True)                     # mny_aug_item
+SAMPLE = np.dtype([("first_item", np.int32), ("n_items", np.int32), ("canvas_slot", np.int32), ("reserved", np.int32)])
+assert ITEM.itemsize == 392 and SAMPLE.itemsize == 16
+
+
+def hue_shift_u8(f):
+    """torchvision adjust_hue: np.array(f * 255).astype(np.uint8) — truncate toward zero, wrap mod 256."""
+    return int(math.trunc(f * 255.0)) % 256
+
+
+def gamma_map(g):
+    """torchvision adjust_gamma (gain 1): the point() table."""
+    return np.array([int((255 + 1 - 1e-3) * 1 * pow(v / 255.0, g)) for v in range(256)], np.uint8)
+
+
+def _jaccard(set_1, set_2):
+    """utils/iou.py find_jaccard_overlap, the same torch ops in the same order."""
+    lower = torch.max(set_1[:, :2].unsqueeze(1), set_2[:, :2].unsqueeze(0))
+    upper = torch.min(set_1[:, 2:].unsqueeze(1), set_2[:, 2:].unsqueeze(0))
+    dims = torch.clamp(upper - lower, min=0)
+    inter = dims[:, :, 0] * dims[:, :, 1]
+    a1 = (set_1[:, 2] - set_1[:, 0]) * (set_1[:, 3] - set_1[:, 1])
+    a2 = (set_2[:, 2] - set_2[:, 0]) * (set_2[:, 3] - set_2[:, 1])
+    return inter / (a1.unsqueeze(1) + a2.unsqueeze(0) - inter)
+
+
+class TrainAugment:
+    """aug = TrainAugment.from_config(config)
+       images, targets, count = aug(groups)     # groups: [[(uint8 HWC RGB array, target [n,5] cls,cx,cy,w,h)] * 1..4]
+    -> images [N,3,H,W] fp32 on `device`, targets a list of CPU [n,5] float32, count = number of decoded images."""
+
+    def __init__(self, train_img_size, mean, std, expand_scale, canvas=1000, device="cuda:0", rng=random):
+        self.sizes = [tuple(int(v) for v in s) for s in train_img_size]
+        self.mean = (ctypes.c_float * 3)(*[float(v) for v in mean])
+        self.std = (ctypes.c_float * 3)(*[float(v) for v in std])
+        self.expand_scale = float(expand_scale)
+        self.canvas = int(canvas)                   # folder2lmdb.py:172 Mosaic(group, [1000, 1000]); square only
+        self.device = torch.device(device)
+        self.rng = rng                              # the reference draws from the global `random`
+        self._packer = BatchPrep(self.sizes, [0, 0, 0], [1, 1, 1], device=device)
+        self._status = None
+
+    @classmethod
+    def from_config(cls, cfg, **kw):
+        if "seg" in cfg:
+            raise ValueError("TrainAugment: configs with a `seg:` section are not supported (the seg-map path, cv2 INTER_AREA "
+                             "resize of the per-class maps, is not implemented on the device)")
+        return cls(cfg["train_img_size"], cfg["normalize"]["mean"], cfg["normalize"]["std"], cfg["expand_scale"], **kw)
+
+    # ---- host planning (no GPU) -------------------------------------------------------------------------------------
+    def _member(self, h, w, target, expand):
+        """folder2lmdb.py get_single_image around transform_od for one decoded image of size (h, w)."""
+        rng = self.rng
+        t2 = torch.Tensor(np.asarray(target, np.float32).reshape(-1, 5))
+        boxes = t2[..., 1:5]
+        if boxes.shape[0] == 0:
+            boxes2, labels = torch.zeros(0, 4), torch.zeros(0)
+        else:
+            x1 = (boxes[..., 0] - boxes[..., 2] / 2).unsqueeze(1)
+            y1 = (boxes[..., 1] - boxes[..., 3] / 2).unsqueeze(1)
+            x2 = (boxes[..., 0] + boxes[..., 2] / 2).unsqueeze(1)
+            y2 = (boxes[..., 1] + boxes[..., 3] / 2).unsqueeze(1)
+            boxes2 = torch.cat((x1 * w, y1 * h, x2 * w, y2 * h), 1)
+            labels = t2[..., 0]
+        order = [BRIGHTNESS, CONTRAST, SATURATION, HUE, GAMMA]           # photometric_distort
+        rng.shuffle(order)
+        chain = []
+        for op in order:
+            if rng.random() < 0.5:
+                chain.append((op, rng.uniform(-18 / 255., 18 / 255.) if op == HUE else rng.uniform(0.5, 1.5)))
+        exp = (h, w, 0, 0)                                                  # expand_od: (new_h, new_w, top, left)
+        if rng.random() < 0.5 and expand:
+            scale = rng.uniform(1, self.expand_scale)
+            nh, nw = int(scale * h), int(scale * w)
+            left = rng.randint(0, nw - w)
+            top = rng.randint(0, nh - h)
+            boxes2 = boxes2 + torch.FloatTensor([left, top, left, top]).unsqueeze(0)
+            exp = (nh, nw, top, left)
+        gh, gw = exp[0], exp[1]
+        crop, boxes2, labels = self._crop(gh, gw, boxes2, labels)
+        if crop is None:
+            crop = (0, 0, gh, gw)                                           # (top, left, h, w) inside the expanded image
+        gh, gw = crop[2], crop[3]
+        flip = rng.random() < 0.5                                           # flip_od
+        if flip:
+            boxes2[:, 0] = gw - boxes2[:, 0] - 1
+            boxes2[:, 2] = gw - boxes2[:, 2] - 1
+            boxes2 = boxes2[:, [2, 1, 0, 3]]
+        old = torch.FloatTensor([gw, gh, gw, gh]).unsqueeze(0)              # folder2lmdb.py:142-151
+        b = boxes2 / old
+        bw, bh = b[..., 2] - b[..., 0], b[..., 3] - b[..., 1]
+        b = torch.cat(((b[..., 0] + bw / 2).unsqueeze(1), (b[..., 1] + bh / 2).unsqueeze(1), bw.unsqueeze(1), bh.unsqueeze(1)), 1)
+        return dict(chain=chain, exp=exp, crop=crop, flip=flip, geo=(gh, gw), target=torch.cat((labels.unsqueeze(1), b), 1))
+
+    def _crop(self, gh, gw, boxes2, labels):
+        """random_crop_od (image_augmentation.py:54-145): -> (None or (top, left, h, w), boxes, labels)."""
+        rng = self.rng
+        while True:
+            min_overlap = rng.choice([0., .1, .2, .3, .4, .5, None])
+            if min_overlap is None:
+                return None, boxes2, labels
+            for _ in range(50):
+                new_h, new_w = int(rng.uniform(0.5, 1) * gh), int(rng.uniform(0.5, 1) * gw)
+                if not 0.5 < new_h / new_w < 2:
+                    continue
+                left = rng.randint(0, gw - new_w)
+                top = rng.randint(0, gh - new_h)
+                right, bottom = left + new_w, top + new_h
+                cr = torch.FloatTensor([left, top, right, bottom])
+                if boxes2.shape[0] == 0:
+                    return (top, left, new_h, new_w), boxes2, labels
+                if _jaccard(cr.unsqueeze(0), boxes2).squeeze(0).max().item() < min_overlap:
+                    continue
+                c = (boxes2[:, :2] + boxes2[:, 2:]) / 2.
+                inside = (c[:, 0] > left) * (c[:, 0] < right) * (c[:, 1] > top) * (c[:, 1] < bottom)
+                if not inside.any():
+                    continue
+                nb = boxes2[inside, :]
+                nb[:, :2] = torch.max(nb[:, :2], cr[:2])
+                nb[:, :2] -= cr[:2]
+                nb[:, 2:] = torch.min(nb[:, 2:], cr[2:])
+                nb[:, 2:] -= cr[:2]
+                return (top, left, new_h, new_w), nb, labels[inside]
+
+    def _mosaic(self, mems):
+        """generate_mosaic_mask + Mosaic (image_augmentation.py:199-278) on the square canvas."""
+        rng, S, num = self.rng, self.canvas, len(mems)
+        xc = int(rng.uniform(.25, .75) * S)
+        yc = int(rng.uniform(.25, .75) * S)
+        if num == 2:
+            mask = rng.choice([[[0, 0, xc, S], [xc, 0, S, S]], [[0, 0, S, yc], [0, yc, S, S]]])
+        elif num == 3:
+            mask = rng.choice([[[0, 0, S, yc], [0, yc, xc, S], [xc, yc, S, S]], [[0, 0, xc, yc], [xc, 0, S, yc], [0, yc, S, S]],
+                               [[0, 0, xc, S], [xc, 0, S, yc], [xc, yc, S, S]], [[0, 0, xc, yc], [xc, 0, S, S], [0, yc, xc, S]]])
+        else:
+            mask = [[0, 0, xc, yc], [xc, 0, S, yc], [0, yc, xc, S], [xc, yc, S, S]]
+        out = torch.Tensor(0, 5)
+        for m, mem in zip(mask, mems):
+            gh, gw = mem["geo"]
+            width, height = m[2] - m[0], m[3] - m[1]
+            ar_src = gh / gw
+            min_ratio, max_ratio = ar_src * 0.5, ar_src * 2
+            ar_tar = height / width
+            ox = oy = 0
+            if ar_tar < min_ratio:
+                ox = rng.randint(0, int(width - height * (1 / min_ratio)))
+                width = int(height * (1 / min_ratio))
+            if ar_tar > max_ratio:
+                oy = rng.randint(0, int(height - width * max_ratio))
+                height = int(width * max_ratio)
+            mem["tile"] = (m[0] + ox, m[1] + oy, width, height)
+            mem["mask"] = tuple(m)
+            label = mem["target"]
+            if label.size(0):
+                nb = label[..., 1:5]
+                w_scale, h_scale = S / width, S / height
+                nb[..., 0], nb[..., 2] = nb[..., 0] / w_scale, nb[..., 2] / w_scale
+                nb[..., 1], nb[..., 3] = nb[..., 1] / h_scale, nb[..., 3] / h_scale
+                nb[..., 0] = nb[..., 0] + (m[0] + ox) / S
+                nb[..., 1] = nb[..., 1] + (m[1] + oy) / S
+                out = torch.cat((out, torch.cat((label[..., 0].unsqueeze(1), nb), 1)))
+        return out
+
+    def plan(self, groups, size=None):
+        """Host only.  groups: [[(image or (h, w), target)]].  -> dict(items ITEM array (offsets unset), samples SAMPLE
+        array, targets, count, size, n_mosaic, max_h, max_w)."""
+        if len(groups) == 0:
+            raise ValueError("empty batch")
+        members, samples, targets, n_mosaic = [], [], [], 0
+        for gi, g in enumerate(groups):
+            if not 1 <= len(g) <= 4:
+                raise ValueError("a group holds 1 to 4 images, got %d" % len(g))
+            mems = []
+            for im, tgt in g:
+                h, w = (int(im[0]), int(im[1])) if isinstance(im, tuple) else (int(im.shape[0]), int(im.shape[1]))
+                mems.append(self._member(h, w, tgt, len(g) == 1))
+                mems[-1]["src"] = (h, w)
+            if len(g) == 1:
+                targets.append(mems[0]["target"])
+                samples.append((len(members), 1, -1, 0))
+            else:
+                targets.append(self._mosaic(mems))
+                samples.append((len(members), len(g), n_mosaic, 0))
+                n_mosaic += 1
+            for m in mems:
+                m["sample"] = gi
+            members.extend(mems)
+        if size is None:
+            size = self.rng.choice(self.sizes)                           # folder2lmdb.py:227, after every __getitem__
+        items = np.zeros(len(members), ITEM)
+        for it, m in zip(items, members):
+            it["h"], it["w"] = m["src"]
+            it["n_ops"] = len(m["chain"])
+            for k, (op, f) in enumerate(m["chain"]):
+                it["op"][k] = op
+                if op == HUE:
+                    it["hue_shift"] = hue_shift_u8(f)
+                elif op == GAMMA:
+                    it["gamma_map"] = gamma_map(f)
+                else:
+                    it["factor"][k] = f                                   # Image.blend takes a C float
+            it["exp"] = m["exp"]
+            it["crop"] = m["crop"]
+            it["flip"] = int(m["flip"])
+            it["sample"] = m["sample"]
+            if "tile" in m:
+                it["tile"] = m["tile"]
+                it["mask"] = m["mask"]
+        max_h = int(max(items["exp"][:, 0].max(), items["h"].max()))
+        max_w = int(max(items["exp"][:, 1].max(), items["w"].max()))
+        return dict(items=items, samples=np.array(samples, SAMPLE), targets=targets, count=sum(len(g) for g in groups),
+                    size=tuple(int(v) for v in size), n_mosaic=n_mosaic, max_h=max_h, max_w=max_w, members=members)
+
+    # ---- device ---------------------------------------------------------------------------------------------------
+    def run_device(self, src, plan, out=None):
+        """src: the packed uint8 images on the device (plan["items"]["offset"] set)."""
+        items, samples = plan["items"], plan["samples"]
+        oh, ow = plan["size"]
+        n_out = len(samples)
+        if out is None:
+            out = torch.empty(n_out, 3, oh, ow, device=self.device, dtype=torch.float32)
+        args = (len(items), n_out, plan["n_mosaic"], plan["max_h"], plan["max_w"], self.canvas, oh, ow)
+        ws = torch.empty(query("mny_aug_ws_bytes", *args), device=self.device, dtype=torch.uint8)
+        it_dev = torch.from_numpy(items.view(np.uint8).copy()).to(self.device, non_blocking=True)
+        sm_dev = torch.from_numpy(samples.view(np.uint8).copy()).to(self.device, non_blocking=True)
+        p = lambda t: ctypes.c_void_p(t.data_ptr())
+        call("mny_aug_batch", p(src), p(it_dev), len(items), p(sm_dev), n_out, plan["max_h"], plan["max_w"], self.canvas,
+             plan["n_mosaic"], oh, ow, self.mean, self.std, p(out), p(ws), ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
+        self._status = ws[:4].view(torch.int32)
+        self._keep = (src, it_dev, sm_dev, ws)
+        return out
+
+    def pack(self, groups):
+        """-> (pinned uint8 staging view, byte offsets of every image in group order)."""
+        stage, desc, _, _ = self._packer.pack([im for g in groups for im, _ in g])
+        return stage, desc["offset"]
+
+    def __call__(self, groups, size=None):
+        plan = self.plan(groups, size)
+        stage, offsets = self.pack(groups)
+        plan["items"]["offset"] = offsets
+        images = self.run_device(stage.to(self.device, non_blocking=True), plan)
+        return images, plan["targets"], plan["count"]
+
+    def check(self):
+        """Host sync: raise if the last batch held an image or record outside the declared bounds."""
+        if self._status is not None:
+            v = int(self._status.item())
+            if v > 0:
+                raise RuntimeError("augment: image %d is empty, misaligned or larger than the declared maximum" % (v - 1))
+            if v < 0:
+                raise RuntimeError("augment: sample record %d is malformed" % (-v - 1))
