@@ -272,9 +272,13 @@ def make_head(N, g, A, C, n_anchors_all, ignore_thresh, iou_thresh, iou_weightin
     return YoloHead(N, g, A, C, n_anchors_all, ignore_thresh, iou_thresh, iou_weighting)
 
 
-def yolo_loss(head, targets, t_off, anchors_all, mask, hp):
-    """head [N,g,g,A*(5+C)] -> (out7 [7] device tensor, dhead)."""
-    ws = torch.empty(query("mny_yolo_loss_ws_bytes", ctypes.byref(hp), 0), device=head.device, dtype=torch.uint8)
+def yolo_loss(head, targets, t_off, anchors_all, mask, hp, ws=None):
+    """head [N,g,g,A*(5+C)] -> (out7 [7] device tensor, dhead).  `ws`: a caller's uint8 workspace of at least
+    mny_yolo_loss_ws_bytes (its contents do not matter: every field is written before it is read)."""
+    nbytes = query("mny_yolo_loss_ws_bytes", ctypes.byref(hp), 0)
+    if ws is None:
+        ws = torch.empty(nbytes, device=head.device, dtype=torch.uint8)
+    assert ws.dtype == torch.uint8 and ws.is_contiguous() and ws.numel() >= nbytes, "yolo_loss: workspace too small"
     out7 = _new(7, like=head)
     dhead = torch.empty_like(head)
     call("mny_yolo_loss", _p(head), _p(targets), _p(t_off), _p(anchors_all), _p(mask), ctypes.byref(hp),

@@ -158,13 +158,16 @@ def decode_rows(head, spec, img_size, layout="nchw"):
     return [rows[b, keep[b]] for b in range(rows.shape[0])]
 
 
-def loss_forward(head, targets, spec, img_size, layout="nchw"):
+def loss_forward(head, targets, spec, img_size, layout="nchw", skip_outside=False):
     """Training path of YOLOLoss.forward (yolo_loss.py:206-236, get_target :77-178).
 
     head     : tensor (may require grad) in `layout`
     targets  : list (len N) of float32 [n_i,5] = (label 1..C, cx, cy, w, h)
     returns  : (loss, recall, avg_iou, obj, no_obj, cls_score, count_per_image)
                with the same python/tensor types as the reference.
+    skip_outside : a target whose cell index falls outside [0, g) still takes part in the ignore mask but assigns
+               no positive — what the HIP kernel does where the reference raises IndexError at :149 (or, for a
+               negative index, wraps round).  The default keeps the reference's behaviour.
     """
     pred = _as_pred(head, spec, layout)
     n, A, g = pred.shape[0], pred.shape[1], pred.shape[2]
@@ -211,6 +214,8 @@ def loss_forward(head, targets, spec, img_size, layout="nchw"):
         for t in range(len(t_b)):
             gi = int(centre[t, 0])                                   # :136
             gj = int(centre[t, 1])                                   # :137
+            if skip_outside and not (0 <= gi < g and 0 <= gj < g):
+                continue
             mine = a_iou[t][spec.mask]                               # :138
             over = (mine > spec.iou_thresh).tolist()                 # :139
             bn = int(best_anchor[t])
@@ -262,3 +267,81 @@ def loss_forward(head, targets, spec, img_size, layout="nchw"):
         box_loss = torch.sum((x - 1) ** 2 * w / torch.sum(w)) / x.numel()
     loss = loss + box_loss * spec.iou_weighting                      # :234
     return loss, recall, avg_iou, obj_avg, no_obj, cls_avg, count / n
+
+
+def loss_branches(head, targets, spec, img_size, layout="nchw"):
+    """Which branches of loss_forward one input enters, and how far its decisions sit from their thresholds.
+
+    Counts (over the whole batch):
+      pos          target x anchor hits                       dup_cell   second positive on an already positive cell
+      two_cls      ... carrying a class the cell had not seen ign2pos    ignored cell that then becomes positive
+      ignored      cells at or above ignore_thresh            multi_anchor_t  targets hitting more than one anchor of the head
+      recall       positives with iou > ignore_thresh         zero_hit   targets hitting no anchor of this head
+      best_not_mine  targets whose best anchor is another head's     nan  NaN entries of the target x cell IoU table
+      outside      targets whose cell index is outside [0, g) bad_label  labels outside 1..C
+    Margins (min over the batch; inf where nothing is compared):
+      m_ignore     |best_iou - ignore_thresh| over cells      m_recall   |iou(pred, gt) - ignore_thresh| over positives
+      m_anchor     |anchor_iou - iou_thresh| over target x anchors of the head
+      m_argmax     best minus second-best anchor IoU          m_cell     distance of cx*g, cy*g from an integer
+    """
+    with torch.no_grad():
+        pred = _as_pred(head.detach(), spec, layout)
+        n, A, g = pred.shape[0], pred.shape[1], pred.shape[2]
+        boxes, scaled = decode_boxes(pred, torch.sigmoid(pred[..., 0:2]), torch.exp(pred[..., 2:4]), spec, img_size)
+        anchor_boxes = torch.tensor(
+            np.concatenate((np.zeros((len(spec.anchors), 2)), scaled), 1), dtype=torch.float32)
+        st = dict(cells=n * A * g * g, targets=0, pos=0, dup_cell=0, two_cls=0, ign2pos=0, ignored=0, multi_anchor_t=0,
+                  recall=0, zero_hit=0, best_not_mine=0, nan=0, outside=0, bad_label=0)
+        inf = float("inf")
+        m = dict(m_ignore=inf, m_recall=inf, m_anchor=inf, m_argmax=inf, m_cell=inf)
+        for b in range(n):
+            t_b = targets[b]
+            if len(t_b) == 0:
+                continue
+            st["targets"] += len(t_b)
+            gt = cxcywh_to_corners_(t_b[:, 1:].clone())
+            iou = pair_iou(gt, boxes[b].reshape(-1, 4))
+            st["nan"] += int(torch.isnan(iou).sum())
+            best = iou.max(0)[0].view(A, g, g)
+            below = best < spec.ignore_thresh
+            st["ignored"] += int((~below).sum())
+            m["m_ignore"] = min(m["m_ignore"], float((best - spec.ignore_thresh).abs().min()))
+            a_iou = pair_iou(torch.cat((torch.zeros(len(t_b), 2), t_b[:, 3:5]), 1), anchor_boxes)
+            best_anchor = torch.argmax(a_iou, 1)
+            m["m_anchor"] = min(m["m_anchor"], float((a_iou[:, spec.mask] - spec.iou_thresh).abs().min()))
+            top = a_iou.sort(1, descending=True)[0]
+            m["m_argmax"] = min(m["m_argmax"], float((top[:, 0] - top[:, 1]).min()))
+            c = t_b[:, 1:3] * torch.tensor([g, g], dtype=torch.float32)
+            m["m_cell"] = min(m["m_cell"], float(torch.minimum(c - c.floor(), c.ceil() - c).min()))
+            seen = {}
+            for t in range(len(t_b)):
+                gi, gj = int(c[t, 0]), int(c[t, 1])
+                cls = int(t_b[t, 0] - 1)
+                if not 0 <= cls < spec.num_classes:
+                    st["bad_label"] += 1
+                if not (0 <= gi < g and 0 <= gj < g):
+                    st["outside"] += 1
+                    continue
+                over = (a_iou[t][spec.mask] > spec.iou_thresh).tolist()
+                bn = int(best_anchor[t])
+                k_best = spec.mask.index(bn) if bn in spec.mask else -1
+                hits = [k for k in range(A) if k == k_best or over[k]]
+                st["multi_anchor_t"] += len(hits) > 1
+                st["best_not_mine"] += k_best < 0
+                st["zero_hit"] += not hits
+                for k in hits:
+                    st["pos"] += 1
+                    key = (k, gj, gi)
+                    if key in seen:
+                        st["dup_cell"] += 1
+                        st["two_cls"] += cls not in seen[key]
+                        seen[key].add(cls)
+                    else:
+                        seen[key] = {cls}
+                        st["ign2pos"] += not bool(below[k, gj, gi])
+                    _, u = ciou_pair(gt[t][None], boxes[b, k, gj, gi][None])
+                    st["recall"] += bool(u > spec.ignore_thresh)
+                    m["m_recall"] = min(m["m_recall"], abs(float(u) - spec.ignore_thresh))
+        st = {k: int(v) for k, v in st.items()}
+        st.update(m)
+        return st

@@ -1,11 +1,15 @@
 """Detection math on the GPU (loss fwd+bwd, decode+compaction, per-class NMS) through the C ABI,
 against the oracle and the fixtures captured from the real reference."""
+
+import ctypes
 import os
+import time
 
 import numpy as np
 import pytest
 import torch
 
+import crowded_cases as CC
 from oracle import nms_ref, procedural, yolo_ref
 
 pytestmark = pytest.mark.gpu
@@ -82,6 +86,172 @@ def test_loss_all_images_empty(ops):
     out7, dhead = _run_loss(ops, head, tg, specs[0])
     np.testing.assert_allclose(out7, np.array([float(v) for v in ref]), rtol=2e-5, atol=1e-7)
     np.testing.assert_allclose(dhead.numpy(), hr.grad.numpy(), rtol=1e-4, atol=1e-9)
+
+
+# ---- the loss kernels on crowded scenes (tests/crowded_cases.py; branch counts and margins asserted on the CPU by
+# tests/test_oracle_detect.py) ------------------------------------------------------------------------------------------
+def _oracle(head, tg, spec, img, **kw):
+    hr = head.clone().requires_grad_(True)
+    ref = yolo_ref.loss_forward(hr, tg, spec, [img, img], **kw)
+    ref[0].backward()
+    return np.array([float(v) for v in ref]), hr.grad
+
+
+def _assert_loss_equals_oracle(ops, head, tg, spec, img, what, **kw):
+    t0 = time.time()
+    ref7, rgrad = _oracle(head, tg, spec, img, **kw)
+    dt = time.time() - t0
+    out7, dhead = _run_loss(ops, head, tg, spec, img)
+    err7 = np.abs(out7 - ref7) / (np.abs(ref7) + 1e-30)
+    d = (dhead.double() - rgrad.double()).abs()
+    print("%s: oracle %.2f s, out7 max rel err %.2e, dhead max abs err %.2e, max err/(1e-4*|ref|+1e-8) %.3f" % (
+        what, dt, err7.max(), float(d.max()), float((d / (1e-4 * rgrad.double().abs() + 1e-8)).max())))
+    np.testing.assert_allclose(out7, ref7, rtol=2e-5, atol=1e-6, err_msg=what)
+    np.testing.assert_allclose(dhead.numpy(), rgrad.numpy(), rtol=1e-4, atol=1e-8, err_msg=what)
+    return out7, dhead
+
+
+def _assert_off_the_thresholds(head, tg, spec, img, cell=True):
+    """For inputs made inside this file: the same decision margins tests/test_oracle_detect.py asserts for crowded_cases."""
+    br = yolo_ref.loss_branches(head, tg, spec, [img, img])
+    for k in ("m_ignore", "m_recall", "m_anchor", "m_argmax"):
+        assert br[k] >= CC.IOU_DELTA, (k, br[k])
+    assert not cell or br["m_cell"] >= CC.CELL_DELTA, br["m_cell"]
+    return br
+
+
+@pytest.mark.parametrize("cid", sorted(CC.ALL))
+def test_loss_crowded_matches_oracle(ops, cid):
+    """out7 and every element of dL/dhead against the CPU oracle at the file's fp32 tolerances, on scenes with 8-120 repeated-cell
+    positives, cells with two class bits, ignored-then-positive cells, several anchors per target, 100-2500 ignored cells:
+    grids 10/11/13/19 on head 0 and 20/22/38 on head 1, N = 64, the BDD100K head (7 classes, other anchors, 416 input), N = 1,
+    one image with 200 targets, and N = 256 at g = 22 (371 712 cells, beyond the 1024 x 256 threads of pass 1 and the 2048
+    blocks of pass 4: the grid-stride loops).  max_targets = 8 there keeps the oracle's Python loop short: 1091 targets, 555
+    positives, 0.9 s measured (the whole case 1.1 s); all fourteen oracle comparisons of this file's crowded tests together 1.6 s.
+    Measured worst errors over the cases: out7 5.4e-7 relative, dL/dhead 6.3e-10 absolute = 0.036 of its tolerance."""
+    spec, img, head, tg = CC.make(cid)
+    _assert_loss_equals_oracle(ops, head, tg, spec, img, cid)
+
+
+def test_loss_exact_duplicate_targets(ops):
+    """The same target row twice in an image: both are positives of the same cell (count, box gradient and the metrics take
+    both, the weights only one), like the reference's loop."""
+    spec, img, head, tg = CC.make("voc-g10")
+    tg = [torch.cat((t, t[:1], t[-1:])) if len(t) else t for t in tg]
+    br = _assert_off_the_thresholds(head, tg, spec, img)
+    base = yolo_ref.loss_branches(head, CC.make("voc-g10")[3], spec, [img, img])
+    assert br["dup_cell"] > base["dup_cell"] and br["two_cls"] == base["two_cls"]
+    _assert_loss_equals_oracle(ops, head, tg, spec, img, "duplicates")
+
+
+def test_loss_target_centre_outside_the_grid(ops):
+    """cx = 1.0 / cy = 1.0 give cell index g: the reference raises IndexError (yolo_loss.py:149), the kernel lets such a target
+    take part in the ignore mask and assigns no positive — yolo_ref.loss_forward(skip_outside=True).  A slightly negative cx
+    truncates towards zero to cell 0 on both sides and is an ordinary positive."""
+    spec, img, head, tg = CC.make("n1")
+    a = np.array(spec.anchors, np.float32) / img
+    extra = torch.tensor([[3, 1.0, 0.37, a[1][0], a[1][1]], [5, 0.52, 1.0, a[0][0], a[0][1]], [9, 1.0, 1.0, a[2][0], a[2][1]],
+                          [11, -0.004, 0.61, a[1][0] * 1.1, a[1][1] * 0.9]])
+    tg = [torch.cat((tg[0], extra))]
+    br = _assert_off_the_thresholds(head, tg, spec, img, cell=False)
+    assert br["outside"] == 3
+    inside = [torch.cat((CC.make("n1")[3][0], extra[3:]))]
+    out7, _ = _assert_loss_equals_oracle(ops, head, tg, spec, img, "outside", skip_outside=True)
+    assert out7[6] == float(yolo_ref.loss_forward(head, inside, spec, [img, img])[6])      # the three add no positive
+    assert out7[6] > float(yolo_ref.loss_forward(head, CC.make("n1")[3], spec, [img, img])[6])   # the negative cx does
+
+
+def test_loss_labels_outside_1_to_C_skip_the_class_term(ops):
+    """DELIBERATE DIVERGENCE, pinned as a known answer.  A label 0 or C + 1 makes the reference index the confidence slot
+    (label 0: cls = -1 -> slot 0) or fail (C + 1: IndexError).  The kernel documents: such a target is a positive like any
+    other (count, confidence, box term, class weights 1), but sets no class bit and adds nothing to the class score.
+    Known answer: the oracle on the same targets with a valid label L, then for every positive cell of those targets the class-L
+    target 0.95 -> 0.05:  dL/dhead there = grad_valid * (o - 0.05) / (o - 0.95), loss += ((o-0.05)^2 - (o-0.95)^2) / sum_w with
+    sum_w = 2 (o - 0.95) / grad_valid, class score -= o / count.  The targets sit alone in cell (0, 0) of their images."""
+    spec = yolo_ref.specs_from_config(procedural.VOC_CONFIG)[0]
+    N, g, C, L = 4, 11, spec.num_classes, 7
+    T = 5 + C
+    head = torch.randn(N, 3 * T, g, g, generator=torch.Generator().manual_seed(5)) * 0.7
+    tg = procedural.targets(N, seed=15, empty_every=0, boxes_per_image=2)
+    a = np.array(spec.anchors, np.float32) / 352
+    odd = {1: 0, 2: C + 1}
+    valid = [t.clone() for t in tg]
+    for n, lab in odd.items():
+        row = torch.tensor([[L, 0.05, 0.05, a[n][0], a[n][1]]])
+        valid[n] = torch.cat((valid[n], row))
+        row = row.clone()
+        row[0, 0] = lab
+        tg[n] = torch.cat((tg[n], row))
+        assert all(int(q[1] * g) > 0 for q in valid[n][:-1])                               # nobody else in column 0
+    _assert_off_the_thresholds(head, valid, spec, 352)
+    ref7, rgrad = _oracle(head, valid, spec, 352)
+    want7, want = ref7.copy(), rgrad.double().clone()
+    count, hits = ref7[6] * N, 0
+    for n in odd:
+        for k in range(3):
+            if rgrad[n, k * T + 4, 0, 0] >= 0:                                             # not a positive cell
+                continue
+            hits += 1
+            o = 1.0 / (1.0 + np.exp(-float(head[n, k * T + 5 + L - 1, 0, 0])))
+            gv = float(rgrad[n, k * T + 5 + L - 1, 0, 0])
+            sum_w = 2 * (o - 0.95) / gv
+            want[n, k * T + 5 + L - 1, 0, 0] = gv * (o - 0.05) / (o - 0.95)
+            want7[0] += ((o - 0.05) ** 2 - (o - 0.95) ** 2) / sum_w
+            want7[5] -= o / count
+    assert hits >= 2
+    out7, dhead = _run_loss(ops, head, tg, spec)
+    np.testing.assert_allclose(out7, want7, rtol=2e-5, atol=1e-6)
+    np.testing.assert_allclose(dhead.numpy(), want.numpy(), rtol=1e-4, atol=1e-8)
+
+
+def test_loss_image_permutation_permutes_the_gradient_bitwise(ops):
+    """Permuting the images of a crowded batch together with their targets permutes dL/dhead bit for bit: the two scalars every
+    element shares (sum of weights, positive count) are sums of exactly representable integers and everything else is local to
+    an image.  out7 (float sums in another order) within the tuple tolerance.  Catches cross-image indexing without a reference."""
+    spec, img, head, tg = CC.make("voc-g13")
+    perm = [7, 3, 11, 0, 5, 1, 9, 2, 10, 4, 8, 6]
+    out_a, d_a = _run_loss(ops, head, tg, spec, img)
+    out_b, d_b = _run_loss(ops, head[perm].contiguous(), [tg[i] for i in perm], spec, img)
+    assert torch.equal(d_a[perm], d_b)
+    assert float(d_a.abs().sum()) > 0 and len({len(t) for t in tg}) > 3
+    np.testing.assert_allclose(out_b, out_a, rtol=2e-5, atol=1e-6)
+
+
+def test_loss_is_bit_deterministic_and_reads_no_stale_workspace(ops):
+    """Two launches on the same inputs are bit-identical, and so is a launch into a workspace pre-filled with 0xFF (NaN floats,
+    all flag and class bits set): no field of the workspace is read before this call has written it."""
+    spec, img, head, tg = CC.make("voc-g22")
+    N, _, g, _ = head.shape
+    anchors, mask, hp = _head_args(ops, spec, N, g, img)
+    t, off = _pack(tg)
+    h = head.permute(0, 2, 3, 1).contiguous().cuda()
+    o1, d1 = ops.yolo_loss(h, t, off, anchors, mask, hp)
+    o2, d2 = ops.yolo_loss(h, t, off, anchors, mask, hp)
+    ws = torch.full((ops.query("mny_yolo_loss_ws_bytes", ctypes.byref(hp), 0),), 0xFF, dtype=torch.uint8, device="cuda")
+    o3, d3 = ops.yolo_loss(h, t, off, anchors, mask, hp, ws=ws)
+    assert torch.equal(o1, o2) and torch.equal(d1, d2)
+    assert torch.equal(o1, o3) and torch.equal(d1, d3)
+    assert bool(torch.isfinite(o1).all()) and float(d1.abs().sum()) > 0
+
+
+def test_loss_non_finite_logit_gives_nan_where_the_oracle_does(ops):
+    """One tw logit of 100 on a positive cell: exp overflows, the decoded box is (-inf, NaN), its IoU with everything NaN.  The
+    kernel and the oracle must agree on which of the 7 outputs and which gradient elements are NaN, and on every finite value."""
+    spec, img, head, tg = CC.make("voc-g11")
+    _, rgrad = _oracle(head, tg, spec, img)
+    T = spec.attrs
+    conf = rgrad.view(8, 3, T, 11, 11)[:, :, 4]
+    n, k, gj, gi = [int(v) for v in (conf < 0).nonzero()[0]]                               # first positive cell
+    head = head.clone()
+    head[n, k * T + 2, gj, gi] = 100.0
+    ref7, rgrad = _oracle(head, tg, spec, img)
+    out7, dhead = _run_loss(ops, head, tg, spec, img)
+    print("oracle out7", ref7, "kernel out7", out7, "NaN grads oracle/kernel", int(rgrad.isnan().sum()), int(dhead.isnan().sum()))
+    assert np.isnan(ref7).any() and bool(rgrad.isnan().any())
+    assert np.array_equal(np.isnan(out7), np.isnan(ref7))
+    assert torch.equal(dhead.isnan(), rgrad.isnan())
+    np.testing.assert_allclose(np.nan_to_num(out7), np.nan_to_num(ref7), rtol=2e-5, atol=1e-6)
+    np.testing.assert_allclose(np.nan_to_num(dhead.numpy()), np.nan_to_num(rgrad.numpy()), rtol=1e-4, atol=1e-8)
 
 
 def test_decode_matches_reference_fixture(ops):

@@ -158,6 +158,33 @@ def gen_loss_and_decode():
           rows=_np(torch.cat(kept)) if sum(len(k) for k in kept) else np.zeros((0, 7), np.float32))
 
 
+def gen_loss_crowded():
+    """The real YOLOLoss on procedural.crowded_scene for both VOC heads (the voc-g11 / voc-g22 cases of tests/crowded_cases.py):
+    repeated cells, two classes on a cell, ignored-then-positive cells, several anchors per target.  Inputs are regenerated from
+    the seed by the test; their float64 checksums make generator drift visible."""
+    from models.yolo_loss import YOLOLoss
+    from oracle import yolo_ref
+    cfg = procedural.VOC_CONFIG
+    y = cfg["yolo"]
+    out = {}
+    for hi, (N, g, seed) in enumerate(((8, 11, 0), (8, 22, 3))):
+        spec = yolo_ref.specs_from_config(cfg)[hi]
+        head, tg = procedural.crowded_scene(N, g, spec, seed)
+        L = YOLOLoss(y["anchors"], y["mask"][hi], 20, [352, 352], y["ignore_thresh"][hi],
+                     y["iou_thresh"], iou_weighting=cfg["iou_weighting"])
+        L.img_size = [352, 352]
+        h = head.clone().requires_grad_(True)
+        res = L(h, [t.clone() for t in tg])
+        res[0].backward()
+        t_all = torch.cat(tg)
+        out["case%d" % hi] = np.array([N, g, seed])
+        out["tuple%d" % hi] = np.array([float(v) for v in res], dtype=np.float64)
+        out["grad%d" % hi] = _np(h.grad)
+        out["sum%d" % hi] = np.array([head.double().sum().item(), head.double().abs().sum().item(),
+                                      t_all.double().sum().item(), (t_all.double() ** 2).sum().item(), float(len(t_all))])
+    _save("loss_crowded.npz", **out)
+
+
 def gen_net():
     cfg = yaml.safe_load(open(os.path.join(REF, "models", "voc", "config.yaml")))
     m = _ref_model(cfg)
@@ -277,6 +304,9 @@ def gen_net_v3():
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
     _install_stubs()
+    if "--only-loss-crowded" in sys.argv:
+        gen_loss_crowded()
+        sys.exit(0)
     if "--only-v3" not in sys.argv:
-        gen_state_keys(); gen_iou_tables(); gen_loss_and_decode(); gen_net()
+        gen_state_keys(); gen_iou_tables(); gen_loss_and_decode(); gen_loss_crowded(); gen_net()
     gen_net_v3()
