@@ -31,6 +31,8 @@
 #ifdef __cplusplus
 extern "C" {
 #endif
+/* the library is built with hidden visibility: these declarations are all it exports */
+#pragma GCC visibility push(default)
 
 #define MNY_OK 0
 #define MNY_EINVAL (-1)   /* bad argument (shape, alignment, null pointer) */
@@ -769,6 +771,7 @@ int mny_gate_bwd3_bf16(const void* y3, const float* s3, const float* b3, const v
                        const float* mean3, const float* invstd3, void* dt, float* dw1_parts, float* red3, int64_t M, int C, int R,
                        void* stream);
 
+#pragma GCC visibility pop
 #ifdef __cplusplus
 }
 #endif

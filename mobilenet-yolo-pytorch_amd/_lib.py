@@ -4,8 +4,10 @@ import ctypes
 import os
 from ctypes import c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_size_t, c_void_p
 
+from . import switches
+
 HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("MNY_LIB") or os.path.join(HERE, "libmnyolo.so")     # MNY_LIB: A/B another build on the same GPU box
+LIB_PATH = switches.get("MNY_LIB") or os.path.join(HERE, "libmnyolo.so")     # MNY_LIB: A/B another build on the same GPU box
 
 ACT_NONE, ACT_RELU6, ACT_LEAKY, ACT_RELU, ACT_HSWISH, ACT_HSIGMOID = 0, 1, 2, 3, 4, 5
 ROUTE_TILE_V1, ROUTE_DMA_F32, ROUTE_DMA_X6, ROUTE_THIN, ROUTE_WIDE, ROUTE_WGRAD_STREAM, ROUTE_WAVE16 = 0, 1, 2, 3, 4, 5, 6      # mny_pw_route
@@ -176,6 +178,7 @@ def load():
         if not os.path.exists(LIB_PATH):
             raise MnyError("libmnyolo.so not found at %s — run __graft_entry__.build() (hipcc, gfx950). "
                            "There is no CPU fallback." % LIB_PATH)
+        switches.warn_unknown()          # a retired or misspelled MNY_* variable is loud, once per process
         lib = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in _SIGS.items():
             fn = getattr(lib, name)

@@ -10,7 +10,9 @@ OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libmnyolo.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
-BASE_FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
+# hidden visibility: the library exports the C ABI of include/mnyolo.h (which pushes default visibility) and nothing else
+BASE_FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
+              "-fvisibility=hidden", "-fvisibility-inlines-hidden"]
 # detect.hip must round like the CPU kernels it replaces (bit-exact NMS): no FMA contraction there
 EXTRA = {"detect.hip": ["-ffp-contract=off"], "evalmap.hip": ["-ffp-contract=off"], "prep.hip": ["-ffp-contract=off"],
          "augment.hip": ["-ffp-contract=off"]}
@@ -47,7 +49,7 @@ def build(force=False, verbose=False):
         with ThreadPoolExecutor(max_workers=min(4, len(jobs))) as ex:
             list(ex.map(run, jobs))
     if jobs or force or _stale(LIB, objs):
-        run([HIPCC, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", LIB] + objs)
+        run([HIPCC, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-fvisibility=hidden", "-Wl,--exclude-libs,ALL", "-o", LIB] + objs)
     return LIB
 
 

@@ -178,6 +178,42 @@ __device__ __forceinline__ void static_for(F&& f) {
 template <int N>
 __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
+// ---- run-time switches ----------------------------------------------------------------------------------------------
+// Every MNY_* environment variable the library reads: X(id, name, type, default, latch, meaning).  The Python side keeps the same rows in
+// switches.py (tests/test_abi.py holds the two together) and warns about any other MNY_* variable it finds set.
+//   kFlag: on when set to anything but "" or "0";  kInt: atoi of the value, `default` when unset;  kWord: first character of the value (0 unset).
+//   latch = 1: read once per process, at the first sw() call; latch = 0: read at every call (the two switches a test flips inside one process).
+#define MNY_SWITCHES(X)                                                                                                              \
+    X(GEMM_V1, "MNY_GEMM_V1", kFlag, 0, 1, "pointwise forward / data gradients on the first-generation tile kernels")                \
+    X(WGRAD_V1, "MNY_WGRAD_V1", kFlag, 0, 1, "pointwise weight gradients on the first-generation tile kernel")                       \
+    X(WGRAD_NO_XCD, "MNY_WGRAD_NO_XCD", kFlag, 0, 1, "weight-gradient workgroups in plain order, not grouped per XCD")               \
+    X(X6, "MNY_X6", kInt, -1, 1, "six-product bf16 GEMM: 0 = never (fp32 MFMA), 1 = wherever supported, -1 = per-shape rule")        \
+    X(NO_W6, "MNY_NO_W6", kFlag, 0, 1, "no pre-cut weight operand for the six-product GEMM")                                         \
+    X(NO_WIDE, "MNY_NO_WIDE", kFlag, 0, 1, "no barrier-free short-reduction kernel (pwwide.hip)")                                    \
+    X(NO_WGS, "MNY_NO_WGS", kFlag, 0, 1, "no stream weight-gradient kernel (pwwgs.hip)")                                             \
+    X(NO_THIN, "MNY_NO_THIN", kFlag, 0, 1, "no vector-ALU kernel for K = 8..32 (pwthin.hip)")                                        \
+    X(NO_PWT, "MNY_NO_PWT", kFlag, 0, 1, "no wave-per-16-pixels thin pointwise kernel (gate.hip)")                                   \
+    X(NO_PWE, "MNY_NO_PWE", kFlag, 0, 1, "no wave form of the thin expand unit backward (gate.hip)")                                 \
+    X(NO_PJBWD, "MNY_NO_PJBWD", kFlag, 0, 1, "no fused projection backward (pjbwd.hip, gate.hip)")                                   \
+    X(NO_LR, "MNY_NO_LR", kFlag, 0, 1, "no low-rank BatchNorm backward of the wide expand units (lrbwd.hip)")                        \
+    X(NO_EXDW, "MNY_NO_EXDW", kFlag, 0, 1, "no fused expand + depthwise unit: the materialised path")                                \
+    X(EXDW_STATS, "MNY_EXDW_STATS", kWord, 0, 0, "gram (default) | direct: how mny_exdw_stats forms its sums")                       \
+    X(NO_STEMDW, "MNY_NO_STEMDW", kFlag, 0, 1, "no fused stem + depthwise backward (stemdw.hip)")                                    \
+    X(STEM_WGRAD_VALU, "MNY_STEM_WGRAD_VALU", kFlag, 0, 1, "stem weight gradient on the vector ALU, not the matrix cores")           \
+    X(DW_V1, "MNY_DW_V1", kFlag, 0, 1, "3x3 depthwise forward on the first-generation sliding-window kernel")                        \
+    X(NO_DWT5, "MNY_NO_DWT5", kFlag, 0, 1, "no tile form of the 5x5 depthwise unit backward")                                        \
+    X(DWT3, "MNY_DWT3", kInt, -1, 1, "tile form of the 3x3 depthwise unit backward: 0 / 1, -1 = per-shape rule")                     \
+    X(DWTF, "MNY_DWTF", kInt, -1, 1, "tile form of the depthwise forward: 0 / 1, -1 = per-shape rule")                               \
+    X(NMS_SMALL, "MNY_NMS_SMALL", kFlag, 0, 0, "NMS buckets of any size through the one-workgroup path")
+enum SwitchType { kFlag, kInt, kWord };
+enum Switch {
+#define X(id, name, type, def, latch, doc) SW_##id,
+    MNY_SWITCHES(X)
+#undef X
+    SW_COUNT
+};
+int sw(Switch id);      // core.hip: the only getenv of the library
+
 // Channel-group thread layout shared by the NHWC stencil / elementwise kernels:
 // a thread owns 4 consecutive channels; `cgb` channel groups per block (<=256), `ppb` pixels per block.
 struct CgLayout {
@@ -203,10 +239,7 @@ inline CgLayout make_cg_layout(int C) {
 // their input.  Channels are independent, so wide layers are split into channel chunks of <= `max_cgb` groups (grid.y) and a
 // block spans >= 256/max_cgb columns: halo ratio (ppb + 2) / ppb.  Measured (same box, ms/step dw_bnbwd + dw_fwd + s2 kernels):
 // 256: 13.0, 64: 12.1, 32: 12.8, 16: 13.3 -> 64 (narrower chunks lose more in per-pixel contiguity than they save in halo).
-// MNY_STENCIL_CGB overrides max_cgb (profiling).
 inline CgLayout make_stencil_layout(int C, int max_cgb = 64) {
-    static const int env = getenv("MNY_STENCIL_CGB") ? atoi(getenv("MNY_STENCIL_CGB")) : 0;
-    if (env > 0) max_cgb = env;
     CgLayout L;
     L.cg_total = C / 4;
     L.chunks = (int)cdiv(L.cg_total, max_cgb);

@@ -18,6 +18,24 @@ void set_error(const char* fmt, ...) {
     va_end(ap);
 }
 
+struct SwitchInfo { const char* name; SwitchType type; int def; bool latch; };
+static const SwitchInfo kSwitches[SW_COUNT] = {
+#define X(id, name, type, def, latch, doc) {name, type, def, latch != 0},
+    MNY_SWITCHES(X)
+#undef X
+};
+static int read_switch(const SwitchInfo& s) {
+    const char* e = getenv(s.name);
+    if (s.type == kInt) return e && *e ? atoi(e) : s.def;
+    if (s.type == kWord) return e ? e[0] : 0;
+    return e && *e && strcmp(e, "0") != 0;
+}
+struct Latched { int v[SW_COUNT]; Latched() { for (int i = 0; i < SW_COUNT; ++i) v[i] = read_switch(kSwitches[i]); } };
+int sw(Switch id) {
+    static const Latched latched;
+    return kSwitches[id].latch ? latched.v[id] : read_switch(kSwitches[id]);
+}
+
 int check_launch(const char* what) {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {

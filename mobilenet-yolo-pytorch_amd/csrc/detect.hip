@@ -914,7 +914,7 @@ extern "C" int mny_yolo_decode(const float* head, const float* anchors_all, cons
 
 
 // large-bucket path (bit-matrix): taken when the segments average more than 2048 rows
-static bool nms_large(int S, int capacity) { return capacity > 2048 * S && getenv("MNY_NMS_SMALL") == nullptr; }
+static bool nms_large(int S, int capacity) { return capacity > 2048 * S && !sw(SW_NMS_SMALL); }
 
 extern "C" size_t mny_nms_ws_bytes(int S, int capacity, int num_classes) {
     if (S <= 0 || capacity < 0 || num_classes <= 0) return 0;

@@ -448,7 +448,7 @@ static int dwb2_geom(DwbGeom& g, CgLayout& L, int& gx, int N, int H, int W, int 
     MNY_REQUIRE(N > 0 && H > 0 && W > 0, "dw_bnbwd_s2: empty tensor");
     g.N = N; g.H = H; g.W = W; g.C = C; g.dz = 0;
     const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
-    static const int th2 = getenv("MNY_DWB2_TH") ? atoi(getenv("MNY_DWB2_TH")) : 16;     // quad rows per strip (the 4 launches of a step: 8: 2.33, 16: 2.30, 32: 2.42, 64: 2.50 ms)
+    constexpr int th2 = 16;     // quad rows per strip (the 4 launches of a step: 8: 2.33, 16: 2.30, 32: 2.42, 64: 2.50 ms)
     const int ns = (int)cdiv(Ho, th2);
     g.TH = (int)cdiv(Ho, ns);
     g.nHS = (int)cdiv(Ho, g.TH);
@@ -456,7 +456,7 @@ static int dwb2_geom(DwbGeom& g, CgLayout& L, int& gx, int N, int H, int W, int 
     L = make_stencil_layout(C);
     g.cg_total = L.cg_total; g.cgb = L.cgb;
     int64_t want = cdiv(g.nstrips, L.ppb);
-    static const int res2 = getenv("MNY_DWB_RES") ? atoi(getenv("MNY_DWB_RES")) : 768;       // resident workgroups (3 per CU at <= 168 VGPRs)
+    constexpr int res2 = 768;       // resident workgroups (3 per CU at <= 168 VGPRs)
     int cap = res2 / L.chunks > 0 ? res2 / L.chunks : 1;
     g.xcd = 1;
     if (cap > 8) cap &= ~7;
@@ -740,19 +740,19 @@ static int dwb5_geom(DwbGeom& g, int& chunks, int& threads, int& gx, int N, int 
     MNY_REQUIRE(N > 0 && H > 0 && W > 0, "dw_bnbwd_s2k5: empty tensor");
     g.N = N; g.H = H; g.W = W; g.C = C; g.dz = 0;
     const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
-    static const int th5 = getenv("MNY_DWB5_TH") ? atoi(getenv("MNY_DWB5_TH")) : 16;
+    constexpr int th5 = 16;
     const int ns = (int)cdiv(Ho, th5);
     g.TH = (int)cdiv(Ho, ns);
     g.nHS = (int)cdiv(Ho, g.TH);
     g.nstrips = (int64_t)N * Wo * g.nHS;
     g.cg_total = C / 2;
-    static const int cgb5 = getenv("MNY_DWB5_CGB") ? atoi(getenv("MNY_DWB5_CGB")) : 64;
+    constexpr int cgb5 = 64;
     chunks = (int)cdiv(g.cg_total, cgb5);
     g.cgb = (int)cdiv(g.cg_total, chunks);
     const int ppb = 256 / g.cgb > 0 ? 256 / g.cgb : 1;
     threads = g.cgb * ppb;
     int64_t want = cdiv(g.nstrips, ppb);
-    static const int res5 = getenv("MNY_DWB5_RES") ? atoi(getenv("MNY_DWB5_RES")) : 768;
+    constexpr int res5 = 768;
     int cap = res5 / chunks > 0 ? res5 / chunks : 1;
     g.xcd = 1;
     if (cap > 8) cap &= ~7;
@@ -799,7 +799,7 @@ static int dwb_geom(DwbGeom& g, CgLayout& L, int& gx, int N, int H, int W, int C
     MNY_REQUIRE(C % 4 == 0 && C > 0, "dw_bnbwd: C=%d must be a positive multiple of 4", C);
     MNY_REQUIRE(N > 0 && H > 0 && W > 0, "dw_bnbwd: empty tensor");
     g.N = N; g.H = H; g.W = W; g.C = C; g.dz = 0;
-    static const int th = getenv("MNY_DWB_TH") ? atoi(getenv("MNY_DWB_TH")) : 32;   // strip height (3 halo rows per strip): 16 -> 32: 5.32 -> 5.22 ms
+    constexpr int th = 32;   // strip height (3 halo rows per strip): 16 -> 32: 5.32 -> 5.22 ms
     const int ns = (int)cdiv(H, th);
     g.TH = (int)cdiv(H, ns);
     g.nHS = (int)cdiv(H, g.TH);
@@ -807,10 +807,9 @@ static int dwb_geom(DwbGeom& g, CgLayout& L, int& gx, int N, int H, int W, int C
     L = make_stencil_layout(C);                            // <= 64 channel groups per block: >= 4 columns, <= 16 KB of LDS constants
     g.cg_total = L.cg_total; g.cgb = L.cgb;
     int64_t want = cdiv(g.nstrips, L.ppb);
-    static const int res1 = getenv("MNY_DWB_RES") ? atoi(getenv("MNY_DWB_RES")) : 768;
+    constexpr int res1 = 768;
     int cap = res1 / L.chunks > 0 ? res1 / L.chunks : 1;       // 3 resident workgroups per CU (<= 168 VGPRs): one full wave of blocks
-    static const int xcd_env = getenv("MNY_DWB_XCD") ? atoi(getenv("MNY_DWB_XCD")) : 1;
-    g.xcd = xcd_env;
+    g.xcd = 1;
     if (cap > 8) cap &= ~7;
     if (want > 8) want = (want + 7) & ~(int64_t)7;
     gx = (int)(want < cap ? want : cap);

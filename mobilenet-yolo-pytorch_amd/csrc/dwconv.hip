@@ -663,44 +663,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 8))) voi
     }
 }
 
-// stride-2 backward-data as a gather over the (at most ceil(K/2)^2) contributing taps
-template <typename T, int KS>
-__global__ __launch_bounds__(256) void dw_bwd_data_s2_kernel(const T* __restrict__ dy, const float* __restrict__ w,
-                                                             const T* __restrict__ addend, T* __restrict__ dx,
-                                                             int N, int H, int W, int C, int Ho, int Wo, int cgb, int cg_total) {
-    constexpr int P = KS / 2;
-    constexpr int KK = KS * KS;
-    const int cgl = threadIdx.x % cgb, pix = threadIdx.x / cgb, ppb = blockDim.x / cgb;
-    const int cg = blockIdx.y * cgb + cgl;
-    if (cg >= cg_total) return;
-    const int c = cg * 4;
-    float4 wg[KK];
-    load_weights<KS>(w, c, false, wg);
-    const int64_t npix = (int64_t)N * H * W;
-    for (int64_t p = (int64_t)blockIdx.x * ppb + pix; p < npix; p += (int64_t)gridDim.x * ppb) {
-        const int wi = (int)(p % W);
-        const int hi = (int)((p / W) % H);
-        const int n = (int)(p / ((int64_t)W * H));
-        float4 out = addend ? ld4(addend + p * C + c) : f4zero();
-#pragma unroll
-        for (int kh = 0; kh < KS; ++kh) {
-            const int th = hi + P - kh;
-            if (th < 0 || (th & 1)) continue;
-            const int ho = th >> 1;
-            if (ho >= Ho) continue;
-#pragma unroll
-            for (int kw = 0; kw < KS; ++kw) {
-                const int tw = wi + P - kw;
-                if (tw < 0 || (tw & 1)) continue;
-                const int wo = tw >> 1;
-                if (wo >= Wo) continue;
-                fma4(out, ld4(dy + (((int64_t)n * Ho + ho) * Wo + wo) * C + c), wg[kh * KS + kw]);
-            }
-        }
-        st4(dx + p * C + c, out);
-    }
-}
-
 // 3x3 stride-2 backward-data, branch-free: a thread owns the 2x2 input quad (2i..2i+1, 2j..2j+1) of 4 channels.  With
 // pad 1 the quad depends on exactly dy[i..i+1][j..j+1], each with a statically known filter tap:
 //   dx[2i  ][2j  ] = dy[i][j]*w11
@@ -809,7 +771,7 @@ __global__ __launch_bounds__(256) void dw_bwd_data_s2k5_kernel(const T* __restri
 }
 
 static bool dw_use_v2(int K, int mode) {
-    static const bool v1 = getenv("MNY_DW_V1") != nullptr;       // A/B: the first-generation sliding-window kernel
+    const bool v1 = sw(SW_DW_V1);       // A/B: the first-generation sliding-window kernel
     return ((K == 3 || K == 5) && mode == 0 && !v1) || (K == 5 && mode == 1 && !v1);      // 5x5 weight gradient: dw5_wgrad_kernel
 }
 
@@ -827,33 +789,12 @@ static int dw_geom(DwGeom& g, CgLayout& L, int& gx, int N, int H, int W, int C, 
     // gx * chunks workgroups = one resident round: 4 per CU (first generation, <= 128 VGPRs), 3 per CU for the second-generation
     // forward (<= 168 VGPRs: the h-swish / leaky variants spilled inside the row loop at 128; tools/probe/dw_probe.hip shows 2, 3
     // and 4 waves per SIMD stream at the same rate)
-    static const int res_env = getenv("MNY_DW_RES") ? atoi(getenv("MNY_DW_RES")) : 768;
-    const int resident = dw_use_v2(K, mode) ? (K == 5 ? 512 : res_env) : kMaxParts;          // 5x5: ~170 VGPRs, two workgroups per CU
+    const int resident = dw_use_v2(K, mode) ? (K == 5 ? 512 : 768) : kMaxParts;          // 5x5: ~170 VGPRs, two workgroups per CU
     int cap = resident / L.chunks > 0 ? resident / L.chunks : 1;
     if (cap > 8) cap &= ~7;                                               // whole XCD rounds (workgroup b runs on XCD b % 8)
-    static const int th_env = getenv("MNY_DW_TH") ? atoi(getenv("MNY_DW_TH")) : 0;          // > 0: strip height; -1: balance search
-    static const int xcd_env = getenv("MNY_DW_XCD") ? atoi(getenv("MNY_DW_XCD")) : 1;
-    static const int nt_env = getenv("MNY_DW_NT") ? atoi(getenv("MNY_DW_NT")) : 1;
-    g.xcd = xcd_env;
-    g.nt = nt_env;
-    int ns;
-    if (dw_use_v2(K, mode) && th_env < 0) {
-        // strips per column: a workgroup walks ceil(want / cap) strips, the last round partly empty, and every strip pays
-        // (K - stride) halo rows of loads without an output row -> pick the split with the best product of both efficiencies
-        double best = -1.0;
-        ns = 1;
-        for (int cand = 1; cand <= g.Ho && g.Ho / cand >= 4; ++cand) {
-            const int th = (int)cdiv(g.Ho, cand);
-            const int64_t want = cdiv((int64_t)N * g.Wo * cdiv(g.Ho, th), L.ppb);
-            const double rounds = (double)want / cap;
-            const double fill = rounds <= 1.0 ? 1.0 : rounds / (double)cdiv(want, cap);
-            const double eff = fill * th / (th + (K - stride) * 0.75);
-            if (eff > best + 1e-9) { best = eff; ns = cand; }
-        }
-    } else {
-        const int th = th_env > 0 ? th_env : 16;                          // first generation: 16 re-reads 2/16 halo rows (8: 2/8); 4.15 -> 4.05 ms
-        ns = (int)cdiv(g.Ho, th);
-    }
+    g.xcd = 1;
+    g.nt = 1;
+    const int ns = (int)cdiv(g.Ho, 16);                                   // strip height: 16 re-reads 2/16 halo rows (8: 2/8); 4.15 -> 4.05 ms
     g.TH = (int)cdiv(g.Ho, ns);
     g.nHS = (int)cdiv(g.Ho, g.TH);
     g.nstrips = (int64_t)N * g.Wo * g.nHS;
@@ -882,24 +823,17 @@ static int dw_launch(const T* x, const float* sc, const float* sh, int act, cons
     }
     if (MODE == 0 && dw_use_v2(K, MODE) && (addend == nullptr || (sc == nullptr && act == MNY_ACT_NONE))) {     // an addend only occurs without a view (backward-data)
         const int xf2 = (sc == nullptr && act == MNY_ACT_NONE) ? 0 : (act == MNY_ACT_RELU6 ? 1 : (act == MNY_ACT_HSWISH ? 2 : 4));
-        // rows requested one step ahead (PF = 1): default for bf16 storage (8-B lanes: see dw_raw); MNY_DW_PF=0/1 forces it for both storage types
-        static const int pf_env = getenv("MNY_DW_PF") ? atoi(getenv("MNY_DW_PF")) : -1;
-        const int pf = pf_env >= 0 ? (pf_env != 0) : (std::is_same<T, bf16_t>::value ? 1 : 0);
-#define MNY_DW2P(S_, X_, A_, N_) do { if (pf) hipLaunchKernelGGL((dw3_fwd_kernel<T, S_, X_, A_, N_, 1>), grid, block, 0, st, x, sc, sh, act, w, flip, addend, y, parts, g); \
-        else hipLaunchKernelGGL((dw3_fwd_kernel<T, S_, X_, A_, N_, 0>), grid, block, 0, st, x, sc, sh, act, w, flip, addend, y, parts, g); } while (0)
-#define MNY_DW2(S_, X_, A_) do { if (g.nt) MNY_DW2P(S_, X_, A_, true); else MNY_DW2P(S_, X_, A_, false); } while (0)
+        // rows requested one step ahead (PF = 1) for bf16 storage (8-B lanes: see dw_raw); output stores non-temporal (NT)
+        constexpr int PF = std::is_same<T, bf16_t>::value ? 1 : 0;
+#define MNY_DW2(S_, X_, A_) hipLaunchKernelGGL((dw3_fwd_kernel<T, S_, X_, A_, true, PF>), grid, block, 0, st, x, sc, sh, act, w, flip, addend, y, parts, g)
 #define MNY_DW2S(S_) do { if (xf2 == 0) { if (addend) MNY_DW2(S_, 0, true); else MNY_DW2(S_, 0, false); } else if (xf2 == 1) MNY_DW2(S_, 1, false); \
         else if (xf2 == 2) MNY_DW2(S_, 2, false); else MNY_DW2(S_, 4, false); } while (0)
         if (K == 3) { if (stride == 1) MNY_DW2S(1); else MNY_DW2S(2); }
 #undef MNY_DW2
-#undef MNY_DW2P
-#define MNY_DW2P(S_, X_, A_, N_) do { if (pf) hipLaunchKernelGGL((dw5_fwd_kernel<T, S_, X_, A_, N_, 1>), grid, block, 0, st, x, sc, sh, act, w, flip, addend, y, parts, g); \
-        else hipLaunchKernelGGL((dw5_fwd_kernel<T, S_, X_, A_, N_, 0>), grid, block, 0, st, x, sc, sh, act, w, flip, addend, y, parts, g); } while (0)
-#define MNY_DW2(S_, X_, A_) do { if (g.nt) MNY_DW2P(S_, X_, A_, true); else MNY_DW2P(S_, X_, A_, false); } while (0)
+#define MNY_DW2(S_, X_, A_) hipLaunchKernelGGL((dw5_fwd_kernel<T, S_, X_, A_, true, PF>), grid, block, 0, st, x, sc, sh, act, w, flip, addend, y, parts, g)
         if (K == 5) { if (stride == 1) MNY_DW2S(1); else MNY_DW2S(2); }
 #undef MNY_DW2S
 #undef MNY_DW2
-#undef MNY_DW2P
         return check_launch(K == 3 ? "dw3_fwd_kernel" : "dw5_fwd_kernel");
     }
     const int xf = (sc == nullptr && act == MNY_ACT_NONE) ? 0 : (act == MNY_ACT_HSWISH ? 2 : 1);
@@ -962,17 +896,14 @@ static int dw_bwd_data_impl(const T* dy, const float* w, const T* addend, T* dx,
     const int P = K / 2;
     const int Ho = (H + 2 * P - K) / 2 + 1, Wo = (W + 2 * P - K) / 2 + 1;
     CgLayout L = make_stencil_layout(C);
-    int64_t want = cdiv((int64_t)N * H * W, L.ppb);
-    dim3 grid((unsigned)(want < 8192 ? want : 8192), L.chunks), block(L.threads);
+    dim3 block(L.threads);
     int64_t wq = cdiv((int64_t)N * ((H + 1) / 2) * ((W + 1) / 2), L.ppb);
     dim3 gridq((unsigned)(wq < 8192 ? wq : 8192), L.chunks);
-    static const bool gather5 = getenv("MNY_DW_S2K5_GATHER") != nullptr;      // A/B: the generic parity-gather kernel
     if (K == 3)
         hipLaunchKernelGGL((dw_bwd_data_s2k3_kernel<T>), gridq, block, 0, (hipStream_t)stream, dy, w, addend, dx, N, H, W, C, Ho, Wo, L.cgb, L.cg_total);
-    else if (!gather5)
+    else
         hipLaunchKernelGGL((dw_bwd_data_s2k5_kernel<T>), gridq, block, 0, (hipStream_t)stream, dy, w, addend, dx, N, H, W, C, Ho, Wo, L.cgb, L.cg_total);
-    else hipLaunchKernelGGL((dw_bwd_data_s2_kernel<T, 5>), grid, block, 0, (hipStream_t)stream, dy, w, addend, dx, N, H, W, C, Ho, Wo, L.cgb, L.cg_total);
-    return check_launch("dw_bwd_data_s2_kernel");
+    return check_launch(K == 3 ? "dw_bwd_data_s2k3_kernel" : "dw_bwd_data_s2k5_kernel");
 }
 extern "C" int mny_dw_bwd_data(const float* dy, const float* w, const float* addend, float* dx,
                                int N, int H, int W, int C, int K, int stride, void* stream) {

@@ -701,8 +701,7 @@ static int dwt_geom(DwtGeom& g, int& gx, int& chunks, int& threads, size_t& lds,
     g.CG = CG; g.PC = PC; threads = CG * PT;
     g.nWT = (int)cdiv(W, PC);
     // strip height: balance whole rounds of resident workgroups against the halo rows
-    static const int res = getenv("MNY_DWT_RES") ? atoi(getenv("MNY_DWT_RES")) : 768;
-    static const int force_th = getenv("MNY_DWT_TH") ? atoi(getenv("MNY_DWT_TH")) : 0;
+    constexpr int res = 768;
     int cap = res / chunks > 0 ? res / chunks : 1;
     if (cap > 8) cap &= ~7;
     double bs = -1.0;
@@ -715,7 +714,7 @@ static int dwt_geom(DwtGeom& g, int& gx, int& chunks, int& threads, size_t& lds,
         const double effr = rounds <= 1.0 ? rounds : rounds / (double)cdiv(tiles, cap);
         const double effh = (double)TH / (TH + R);            // 2R halo rows of G, Y per strip = half the streams
         const double sc2 = effr * effh;
-        if (force_th > 0 ? (TH <= force_th && bs < 0) : sc2 > bs) { bs = sc2; bTH = TH; if (force_th > 0) break; }
+        if (sc2 > bs) { bs = sc2; bTH = TH; }
     }
     g.TH = bTH;
     g.nHS = (int)cdiv(H, g.TH);
@@ -736,9 +735,8 @@ static int dwt_geom(DwtGeom& g, int& gx, int& chunks, int& threads, size_t& lds,
 // work the tile form has no idle cycles for).  Channel counts that leave the last workgroup chunk (64 channels) under 3/4 full stay on the register
 // form (C72: 0.304 vs 0.332 ms), fp32 storage too (C384 @22x22: 0.221 vs 0.247 ms).  MNY_DWT3=1 / 0 forces the tile / register form for every 3x3 unit.
 bool dwt_use(int K, int bf, int red, int C) {
-    static const bool no5 = getenv("MNY_NO_DWT5") != nullptr && atoi(getenv("MNY_NO_DWT5")) != 0;
-    static const int env3 = getenv("MNY_DWT3") ? atoi(getenv("MNY_DWT3")) : -1;
-    if (K == 5) return !no5;
+    const int env3 = sw(SW_DWT3);
+    if (K == 5) return !sw(SW_NO_DWT5);
     if (K != 3) return false;
     if (env3 >= 0) return env3 != 0;
     if (!bf) return false;
@@ -807,7 +805,7 @@ int dwt_launch(int bf, const void* g, const void* y, const float* scale, const f
 // C320 @32x32 0.026 -> 0.037: three loads per row are no burden for the register form, the barrier per row is one for the tile form).
 // MNY_DWTF=0 / 1: never / every stride-1 launch (A/B).
 bool dwt_fwd_use(int K, int stride, int bf, int C) {
-    static const int env = getenv("MNY_DWTF") ? atoi(getenv("MNY_DWTF")) : -1;
+    const int env = sw(SW_DWTF);
     if (stride != 1 || (K != 3 && K != 5) || C % 4 != 0) return false;
     if (env >= 0) return env != 0;
     if (!bf || C < 120 || K != 5) return false;

@@ -52,8 +52,7 @@ static ExGeom ex_geom(int N, int H, int W, int K, int C, int th = kExTH) {
 }
 
 static int ex_grid(const ExGeom& g, int per_cu) {
-    static const int env = getenv("MNY_EXDW_GRID") ? atoi(getenv("MNY_EXDW_GRID")) : 0;
-    int cap = env > 0 ? env : 256 * per_cu;
+    const int cap = 256 * per_cu;
     int gx = g.items < cap ? g.items : cap;
     if (gx > 8) gx &= ~7;           // a multiple of 8: the XCD-contiguous item order below needs it
     return gx;
@@ -545,12 +544,12 @@ static int ex_fwd2_launch(const ExFwdArgs& a, bool xf, int grid, hipStream_t st)
 using namespace mny;
 
 extern "C" int mny_exdw_supported(int N, int H, int W, int K, int C, int stride) {
-    static const bool off = getenv("MNY_NO_EXDW") != nullptr;      // A/B switch: the materialised path
+    const bool off = sw(SW_NO_EXDW);      // A/B switch: the materialised path
     return (!off && ex_shape_ok(N, H, W, K, C, stride)) ? 1 : 0;
 }
 
 // MNY_EXDW_STATS=direct (read at every call: a test switches it): the first form, which recomputes Y on the matrix cores and sums it
-static bool ex_stats_gram() { const char* e = getenv("MNY_EXDW_STATS"); return !(e && e[0] == 'd'); }
+static bool ex_stats_gram() { return sw(SW_EXDW_STATS) != 'd'; }      // "direct": the first form (read per call)
 extern "C" int mny_exdw_stat_parts(int64_t M, int K, int C) {
     (void)K; (void)C;
     const int64_t tiles = cdiv(M, kExStatRows);
@@ -1197,14 +1196,12 @@ static int exdw_bwd_impl(const float* gz, const float* z, const float* z_scale, 
     hipStream_t st = (hipStream_t)stream;
     ExBwdArgs a{gz, z, z_scale, z_shift, z_coef, x, in_scale, in_shift, in_act, w_exp, e_scale, e_shift, e_mean, e_invstd, w_dw, e_gamma,
                 ws + o.partials, dw_ws, dx, g};
-    static const int only = getenv("MNY_EXDW_ONLY") ? atoi(getenv("MNY_EXDW_ONLY")) : 0;       // timing aid: 1 = without the thin remainder kernel
     int rc = K == 16 ? ex_bwd1v2_launch<16>(a, xf, grid, st) : (K == 24 ? ex_bwd1v2_launch<24>(a, xf, grid, st) : ex_bwd1v2_launch<32>(a, xf, grid, st));
     if (rc) return rc;
     rc = pw_bnbwd_finalize_launch(ws + o.partials, grid, ws + o.red, w_exp, e_gamma, e_mean, e_invstd, (int64_t)N * H * W, C, K, dw_exp, dgamma_e, dbeta_e,
                                   ws + o.B1, ws + o.Q, ws + o.bias, st);
     if (rc) return rc;
     if (dw_dw) { rc = launch_reduce_parts(dw_ws, grid, C * 9, dw_dw, st); if (rc) return rc; }
-    if (only == 1) return MNY_OK;
     // the pass left dz (ca o W)^T in dx; what depends on the BN-backward sums (Q, bias) is thin and follows
     ExFixArgs f{dx, x, in_scale, in_shift, in_act, ws + o.Q, ws + o.bias, addend, (int64_t)N * H * W, in_mean, in_invstd, in_red};
     return K == 16 ? ex_dxfix_launch<16>(f, xf, st) : (K == 24 ? ex_dxfix_launch<24>(f, xf, st) : ex_dxfix_launch<32>(f, xf, st));

@@ -850,7 +850,7 @@ __global__ __launch_bounds__(256) void pwt_fwd_kernel(PwtArgs p) {
 
 // shapes: K a multiple of 8 up to 48, N a multiple of 8 up to 240, and enough pixels that the vector-ALU / tile kernels are the slower choice
 bool pwt_ok(int64_t M, int K, int N, int in_act, bool has_bias) {
-    static const bool off = getenv("MNY_NO_PWT") != nullptr && atoi(getenv("MNY_NO_PWT")) != 0;
+    const bool off = sw(SW_NO_PWT);
     if (off || has_bias || in_act == MNY_ACT_HSIGMOID) return false;
     if (K <= 0 || N <= 0 || (K & 7) || (N & 7) || K > 48 || N > 240) return false;
     return M >= 131072;
@@ -1156,7 +1156,7 @@ __global__ __launch_bounds__(256) void pwe_dgrad_kernel(PweArgs p) {
 
 // shapes of the wave form: K = 16 / 24 / 32, N <= 80 (five 16-channel tiles: the per-lane sums of stage A fit 2 waves per SIMD; 8 tiles spilled), enough pixels
 bool pwe_ok(int64_t M, int K, int N) {
-    static const bool off = getenv("MNY_NO_PWE") != nullptr && atoi(getenv("MNY_NO_PWE")) != 0;
+    const bool off = sw(SW_NO_PWE);
     return !off && M >= 131072 && (K == 16 || K == 24 || K == 32) && N > K && N <= 80 && (N & 7) == 0;
 }
 static inline int pwe_bw(int K) { return K <= 16 ? 4 : 8; }
@@ -1333,7 +1333,7 @@ extern "C" int mny_gate_bwd3_bf16(const void* y3, const float* s3, const float* 
 }
 
 extern "C" int mny_pj_bwd_supported_bf16(int64_t M, int Ki, int No, int d_act) {
-    static const bool off = getenv("MNY_NO_PJBWD") != nullptr;
+    const bool off = sw(SW_NO_PJBWD);
     return (!off && pj16_shape_ok(M, Ki, No) && d_act != MNY_ACT_HSIGMOID) ? 1 : 0;
 }
 extern "C" int mny_pj_bwd_parts_bf16(int64_t M, int Ki, int No) { return pj16_shape_ok(M, Ki, No) ? pj16_grid(M) : MNY_EINVAL; }

@@ -268,7 +268,7 @@ using namespace mny;
 
 // which (M, K, C) the low-rank form serves: a thin input (K a multiple of 8, <= 320: the Gram band fits LDS) feeding an output at least twice as wide
 extern "C" int mny_lr_supported(int64_t M, int K, int C) {
-    static const bool off = getenv("MNY_NO_LR") != nullptr && atoi(getenv("MNY_NO_LR")) != 0;
+    const bool off = sw(SW_NO_LR);
     return (!off && M > 0 && K >= 16 && K <= 320 && (K & 7) == 0 && C >= 2 * K && C <= 4096) ? 1 : 0;
 }
 extern "C" int mny_lr_gram_parts(int64_t M, int K) { return (M <= 0 || K <= 0 || K > 320) ? MNY_EINVAL : lr_gram_gx(M); }

@@ -213,7 +213,7 @@ static int pj_launch(const PjArgs& a, int grid, hipStream_t st) {
 using namespace mny;
 
 extern "C" int mny_pj_bwd_supported(int64_t M, int Ki, int No, int d_act) {
-    static const bool off = getenv("MNY_NO_PJBWD") != nullptr;
+    const bool off = sw(SW_NO_PJBWD);
     return (!off && pj_shape_ok(M, Ki, No) && d_act != MNY_ACT_HSWISH && d_act != MNY_ACT_HSIGMOID) ? 1 : 0;
 }
 

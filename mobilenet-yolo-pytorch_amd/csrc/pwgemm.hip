@@ -1001,7 +1001,7 @@ static Nt2Kernel nt2_kernel(int TN, int XF, int BF = 0, int X6 = 0) {
 
 // fp32 GEMMs whose matrix-core time exceeds their HBM time take the six-product bf16 form (MNY_X6=0: never, =1: always, for A/B runs)
 static int nt_x6(int64_t M, int K, int N) {
-    static const int env = getenv("MNY_X6") ? atoi(getenv("MNY_X6")) : -1;
+    const int env = sw(SW_X6);
     if (env >= 0) return env != 0;
     const double ai = 2.0 * K * N / (4.0 * (K + N));            // FLOP per byte of the A and C rows
     return ai >= 20.0;                                          // 157 TFLOP/s / 8 TB/s
@@ -1069,8 +1069,7 @@ static int nt2_blocks_per_cu(int TN, int XF, size_t lds, int BF = 0) {
 static Nt2Plan nt2_plan(int64_t M, int K, int N, bool xf, int BF = 0, int tn_cap = 5) {
     Nt2Plan pl;
     int best = 1, best_pad = 1 << 30;
-    static const int max_tn = getenv("MNY_NT_MAXTN") ? atoi(getenv("MNY_NT_MAXTN")) : 5;
-    for (int tn = max_tn < tn_cap ? max_tn : tn_cap; tn >= 1; --tn) {        // minimise the padded width; ties -> the wider tile (A read fewer times,
+    for (int tn = tn_cap; tn >= 1; --tn) {           // minimise the padded width; ties -> the wider tile (A read fewer times,
         int pad = (int)cdiv(N, 32 * tn) * 32 * tn;   // longer contiguous output rows)
         if (pad < best_pad) { best_pad = pad; best = tn; }
     }
@@ -1088,12 +1087,11 @@ static Nt2Plan nt2_plan(int64_t M, int K, int N, bool xf, int BF = 0, int tn_cap
     // (blocks on the busiest CU) x (tiles per block).  Filling every slot (3/CU) with 5.04 tiles' worth of work each means 6
     // rounds on CUs holding 3 blocks = 18 tile-times, where 2 blocks/CU x 8 tiles = 16.  Search tiles-per-block upwards from
     // the one-wave minimum; ties -> more blocks (more waves to hide latency).
-    static const bool balance = getenv("MNY_NT_BALANCE") == nullptr || atoi(getenv("MNY_NT_BALANCE")) != 0;
-    static const double min_ai = getenv("MNY_NT_BALANCE_AI") ? atof(getenv("MNY_NT_BALANCE_AI")) : 100.0;
+    constexpr double min_ai = 100.0;
     // ... for the matrix-pipe-bound shapes only (FLOP per byte of A + C rows): an HBM-bound layer wants every slot filled
     // (memory-level parallelism), measured 5 % slower with fewer, longer blocks
     const double ai = 2.0 * K * N / ((BF ? 2.0 : 4.0) * (K + N));
-    if (balance && ai >= min_ai) {
+    if (ai >= min_ai) {
         const int t_min = pl.tiles_per_block;
         long best_cost = -1;
         int best_t = t_min, best_b = 0;
@@ -1108,8 +1106,6 @@ static Nt2Plan nt2_plan(int64_t M, int K, int N, bool xf, int BF = 0, int tn_cap
     }
     pl.gx = (int)cdiv(pl.m_tiles, pl.tiles_per_block);
     pl.grid = (int)cdiv(pl.gx, 8) * 8 * pl.n_tiles;
-    static const bool plan_debug = getenv("MNY_PLAN_DEBUG") != nullptr;
-    if (plan_debug) fprintf(stderr, "nt2_plan M=%lld K=%d N=%d TN=%d bpc=%d m_tiles=%d n_tiles=%d t=%d gx=%d grid=%d\n", (long long)M, K, N, best, blocks_per_cu, pl.m_tiles, pl.n_tiles, pl.tiles_per_block, pl.gx, pl.grid);
     pl.lds = nt2_lds(best, K, xf, BF);
     return pl;
 }
@@ -1775,19 +1771,17 @@ static int pick_block(int c) {      // 64 or 128: minimise the padded extent, ti
 // either way, so the partial-row count does not depend on which of the two a launch takes.  Measured (bracketed steps, same box): 512 x 512 @
 // M 123 904 0.423 -> 0.399 ms, 1280 -> 512 @ 30 976 0.262 -> 0.248, the 33 weight gradients of the headline step 4.30 -> 4.20 ms
 static bool wg_wide_shape(int64_t M, int K, int N) {
-    static const int env = getenv("MNY_WG_TJ4") ? atoi(getenv("MNY_WG_TJ4")) : 1;     // (=0: the 128 x 128 tile, for A/B runs)
-    return env != 0 && nt_x6(M, K, N) && K % 256 == 0 && N % 128 == 0;
+    return nt_x6(M, K, N) && K % 256 == 0 && N % 128 == 0;
 }
 
 static WgPlan wg_plan(int64_t M, int K, int N, bool bf16 = false, bool wide_ok = false) {
     WgPlan pl;
     const int nco = (int)cdiv(N, 32), nci = (int)cdiv(K, 32);
     int BI, BJ, KC;
-    static const bool slice96 = getenv("MNY_WG_NOSLICE96") == nullptr;
     if (nco * nci <= 6) {
         pl.mode = 1; pl.TI = nco; pl.TJ = nci; BI = 32 * nco; BJ = 32 * nci; KC = bf16 ? 64 : 32;
         pl.gx = pl.gy = 1;
-    } else if (slice96 && !bf16 && ((K == 96 && N >= 192) || (N == 96 && K >= 192))) {
+    } else if (!bf16 && ((K == 96 && N >= 192) || (N == 96 && K >= 192))) {
         // a 96-wide side is 1.5 of the 64-wide units of the 2x2-wave tiles (25-33 % of the MFMAs multiply padding): slice the
         // other side instead and give every workgroup exact 96 x 64 tiles in the all-waves-share-the-tile mode
         pl.mode = 1; KC = 32;
@@ -1799,7 +1793,7 @@ static WgPlan wg_plan(int64_t M, int K, int N, bool bf16 = false, bool wide_ok =
         pl.TI = BI / 64; pl.TJ = BJ / 64;
         pl.gx = (int)cdiv(N, BI); pl.gy = (int)cdiv(K, BJ);
     }
-    static const int wg_blocks = getenv("MNY_WG_BLOCKS") ? atoi(getenv("MNY_WG_BLOCKS")) : 1024;     // (round 6, next to the 128 x 256 tile: 1536 -> 1024: weight gradients 4.00 -> 3.99 ms, their combines 0.34 -> 0.31 ms, 0.4 GB fewer partial rows per step; 768: 4.32 ms)
+    constexpr int wg_blocks = 1024;     // (round 6, next to the 128 x 256 tile: 1536 -> 1024: weight gradients 4.00 -> 3.99 ms, their combines 0.34 -> 0.31 ms, 0.4 GB fewer partial rows per step; 768: 4.32 ms)
     int64_t splits = wg_blocks / ((int64_t)pl.gx * pl.gy);
     if (splits < 1) splits = 1;
     const int64_t max_splits = cdiv(M, 4 * KC);
@@ -1900,175 +1894,8 @@ struct BnwArgs {
 
 // partial layout per split: P1[N*K] | Gram[K*K] | s1[N] | s2[N] | s3[K]   (bnw_stride: common.h — exdw.hip writes the same rows)
 
-template <int TI>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 8))) void pw_bnbwd_stage1_kernel(BnwArgs p) {
-    constexpr int KC = 16, S = 3, BI = 32 * TI, BJ = 32;
-    constexpr int G_ST = KC * BI, X_ST = KC * BJ, STAGE = 2 * G_ST + X_ST;   // floats: G | Y | X
-    constexpr int NG = G_ST / 256, NX = X_ST / 256, NL = 2 * NG + NX;
-    constexpr int LPW = (NL + 3) / 4;
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int li = lane & 31, kk = lane >> 5;
-    const int64_t m_begin = (int64_t)blockIdx.x * p.rows_per_block;
-    const int64_t m_end = min(m_begin + p.rows_per_block, p.M);
-    const bool has_xf = p.xsc != nullptr;
-    const float xslope = act_slope(p.xact), xhi = act_hi(p.xact);
-    const float aslope = act_slope(p.act), ahi = act_hi(p.act);
-    const int krow0 = wave * (KC / 4);
-    const int tile_off = blockIdx.y * TI, n_off = tile_off * 32;      // this block's column slice
-    const bool slice0 = blockIdx.y == 0;                              // Gram / colsum(X) are taken once
-
-    float sc[TI], sh[TI], mu[TI], is[TI], s1[TI], s2[TI];
-#pragma unroll
-    for (int i = 0; i < TI; ++i) {
-        const int co = n_off + i * 32 + li;
-        const bool ok = co < p.N;
-        sc[i] = ok ? p.sc[co] : 0.f; sh[i] = ok ? p.sh[co] : 0.f; mu[i] = ok ? p.mean[co] : 0.f; is[i] = ok ? p.invstd[co] : 0.f;
-        s1[i] = 0.f; s2[i] = 0.f;
-    }
-    const float xs = (has_xf && li < p.K) ? p.xsc[li] : 1.f, xh = (has_xf && li < p.K) ? p.xsh[li] : 0.f;
-    float s3 = 0.f;
-
-    const float* zero_src = reinterpret_cast<const float*>(&mny_zero16);
-    int d_row[LPW], d_lds[LPW], d_kind[LPW];
-    bool d_ok[LPW];
-    int d_off[LPW];
-#pragma unroll
-    for (int i = 0; i < LPW; ++i) {
-        int j = wave + 4 * i;
-        if (j >= NL) j = NL - 1;
-        d_kind[i] = j < NG ? 0 : (j < 2 * NG ? 1 : 2);                    // 0: G, 1: Y, 2: X
-        const int jj = d_kind[i] == 0 ? j : (d_kind[i] == 1 ? j - NG : j - 2 * NG);
-        const int q = jj * 64 + lane;
-        const int W4 = (d_kind[i] == 2 ? BJ : BI) / 4;
-        d_row[i] = q / W4;
-        const int c = (q % W4) * 4;
-        d_lds[i] = (d_kind[i] == 0 ? 0 : (d_kind[i] == 1 ? G_ST : 2 * G_ST)) + jj * 256;
-        d_ok[i] = d_kind[i] == 2 ? c < p.K : n_off + c < p.N;
-        d_off[i] = d_kind[i] == 2 ? c : n_off + c;
-    }
-    auto issue = [&](int64_t m0, int slot) {
-        float* stage = smem + slot * STAGE;
-#pragma unroll
-        for (int i = 0; i < LPW; ++i) {
-            const int64_t m = m0 + d_row[i];
-            const int64_t mc = m < m_end ? m : m_end - 1;
-            const float* src = zero_src;
-            if (d_ok[i]) {
-                if (d_kind[i] == 0) src = m < m_end ? p.G + m * p.N + d_off[i] : zero_src;   // dz = 0 past the slice
-                else if (d_kind[i] == 1) src = p.Y + mc * p.N + d_off[i];
-                else src = p.X + mc * p.K + d_off[i];
-            }
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                             (__attribute__((address_space(3))) void*)(stage + d_lds[i]), 16, 0, 0);
-        }
-    };
-
-    f32x16 acc[TI], gram;
-#pragma unroll
-    for (int i = 0; i < TI; ++i)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) gram[r] = 0.f;
-
-    auto compute = [&](int64_t m0, int slot) {
-        const float* gb = smem + slot * STAGE + (krow0 + kk) * BI + li;
-        const float* yb = gb + G_ST;
-        const float* xb = smem + slot * STAGE + 2 * G_ST + (krow0 + kk) * BJ + li;
-#pragma unroll
-        for (int kp = 0; kp < KC / 8; ++kp) {
-            const bool rok = m0 + krow0 + kp * 2 + kk < m_end;
-            const float xz = fmaf(xb[kp * 2 * BJ], xs, xh);
-            const float b = rok ? fminf(fmaxf(xz, xslope * xz), xhi) : 0.f;     // rows past the slice contribute nothing
-            s3 += b;
-            float af[TI];
-            const int64_t pair = (m0 + krow0 + kp * 2) >> 1;                     // rows (2*pair, 2*pair+1) <-> kk
-#pragma unroll
-            for (int i = 0; i < TI; ++i) {
-                const float g = gb[kp * 2 * BI + i * 32], y = yb[kp * 2 * BI + i * 32];
-                const float z = fmaf(y, sc[i], sh[i]);
-                const bool on = z > 0.f && z < ahi;                                // act' = on ? 1 : slope
-                const unsigned long long bal = __ballot(on);
-                if (lane == 0 && m0 + krow0 + kp * 2 < m_end && tile_off + i < p.tiles_total) p.mask[(int64_t)(tile_off + i) * p.npairs + pair] = bal;
-                const float dz = on ? g : g * aslope;
-                s1[i] += dz;
-                s2[i] = fmaf(dz, (y - mu[i]) * is[i], s2[i]);
-                af[i] = dz;
-            }
-#pragma unroll
-            for (int i = 0; i < TI; ++i) acc[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[i], b, acc[i], 0, 0, 0);
-            if (slice0) gram = __builtin_amdgcn_mfma_f32_32x32x2f32(b, b, gram, 0, 0, 0);
-        }
-    };
-
-    const int total = (int)((m_end - m_begin + KC - 1) / KC);
-    int i_t = 0, i_slot = 0, c_slot = 0, c_t = 0;
-    auto issue_next = [&]() { issue(m_begin + (int64_t)i_t * KC, i_slot); ++i_t; if (++i_slot == S) i_slot = 0; };
-    auto consume = [&]() { compute(m_begin + (int64_t)c_t * KC, c_slot); ++c_t; if (++c_slot == S) c_slot = 0; };
-    const int pre = total < S - 1 ? total : S - 1;
-    for (int t = 0; t < pre; ++t) issue_next();
-    for (int t = 0; t < total - pre; ++t) {
-        wait_vmcnt<LPW*(S - 2)>();
-        __builtin_amdgcn_s_barrier();
-        issue_next();
-        consume();
-    }
-    for (int t = 0; t < pre; ++t) {
-        wait_vmcnt<0>();
-        __builtin_amdgcn_s_barrier();
-        consume();
-    }
-
-    // ---- block reduction over the 4 waves (fixed order) and the two k-halves, then one partial row
-    float* dst = p.partial + (int64_t)blockIdx.x * bnw_stride(p.N, p.K);
-    float* red = smem;                         // [3][16][64]
-    auto reduce_tile = [&](f32x16& t, float* out, int rows, int cols, int ld, int row0) {
-        __syncthreads();
-        if (wave > 0) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) red[((wave - 1) * 16 + r) * 64 + lane] = t[r];
-        }
-        __syncthreads();
-        if (wave == 0) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float v = ((t[r] + red[(0 * 16 + r) * 64 + lane]) + red[(1 * 16 + r) * 64 + lane]) + red[(2 * 16 + r) * 64 + lane];
-                const int row = row0 + (r & 3) + 8 * (r >> 2) + 4 * kk;
-                if (row < rows && li < cols) out[(int64_t)row * ld + li] = v;
-            }
-        }
-    };
-#pragma unroll
-    for (int i = 0; i < TI; ++i) reduce_tile(acc[i], dst, p.N, p.K, p.K, n_off + i * 32);
-    if (slice0) reduce_tile(gram, dst + (int64_t)p.N * p.K, p.K, p.K, p.K, 0);
-    // vectors: lanes l and l^32 hold the same channel
-    __syncthreads();
-    float* vred = smem;                        // [4][2*TI+1][32]
-#pragma unroll
-    for (int i = 0; i < TI; ++i) {
-        const float a = s1[i] + __shfl_xor(s1[i], 32), b2 = s2[i] + __shfl_xor(s2[i], 32);
-        if (kk == 0) { vred[(wave * (2 * TI + 1) + i) * 32 + li] = a; vred[(wave * (2 * TI + 1) + TI + i) * 32 + li] = b2; }
-    }
-    {
-        const float c3 = s3 + __shfl_xor(s3, 32);
-        if (kk == 0) vred[(wave * (2 * TI + 1) + 2 * TI) * 32 + li] = c3;
-    }
-    __syncthreads();
-    float* vdst = dst + (int64_t)p.N * p.K + (int64_t)p.K * p.K;
-    for (int e = tid; e < (2 * TI + 1) * 32; e += 256) {
-        const int v = e / 32, l = e % 32;
-        float a = 0.f;
-        for (int w = 0; w < 4; ++w) a += vred[(w * (2 * TI + 1) + v) * 32 + l];
-        if (v < TI) { const int co = n_off + v * 32 + l; if (co < p.N) vdst[co] = a; }
-        else if (v < 2 * TI) { const int co = n_off + (v - TI) * 32 + l; if (co < p.N) vdst[p.N + co] = a; }
-        else if (l < p.K && slice0) vdst[2 * p.N + l] = a;
-    }
-}
-
 // Stage 1, second generation (round 3).  Same tiling, LDS-DMA ring, lane mapping, partial-row layout and arithmetic (order
-// included: bit-identical results) as pw_bnbwd_stage1_kernel; what changed is the instruction stream.  The counters of the first
+// included: bit-identical results) as the first-generation stage 1 it replaced; what changed is the instruction stream.  The counters of the first
 // generation (profiles/r03_pmc_pw_bnbwd.txt, 16 -> 96 @ 176x176) showed 15 scalar and 20 vector instructions per MFMA, 44 % of the
 // wave cycles stalled at issue and the matrix pipe 30 % busy at 4.45 TB/s: every LDS read sat in its own basic block behind a
 // `lane == 0` mask store (s_cbranch_execz + lgkmcnt(0) per read), the DMA issue went through per-instruction kind / range branches.
@@ -2078,8 +1905,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 8))) voi
 // T: storage type of G, Y, X (float, or bf16_t for bf16-storage plans: the LDS image holds bf16, a 16-byte DMA chunk is 8 elements, the
 // arithmetic is the same fp32; K % 8 == 0 and N % 8 == 0 there)
 // S: ring depth.  A stage is 16 rows whatever the storage type, i.e. HALF the bytes with bf16 storage (2 x 5 KB per workgroup in flight at
-// three stages; the bf16 instantiation runs 2.9 TB/s where the fp32 one runs 4.3-5.2).  Six stages (MNY_BNW_RING=6) were measured in round 5
-// and changed nothing: bytes in flight are not what holds this kernel back.
+// three stages; the bf16 instantiation runs 2.9 TB/s where the fp32 one runs 4.3-5.2).  Six stages were measured in round 5, same box: 15.24 / 15.24
+// vs 15.20 / 15.25 ms — no gain, 3 stays: bytes in flight are not what holds this kernel back.
 template <int TI, typename T = float, int S = 3>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 8))) void pw_bnbwd_stage1b_kernel(BnwArgs p) {
     constexpr int KC = 16, BI = 32 * TI, BJ = 32;
@@ -2812,8 +2639,7 @@ static BnwPlan bnw_plan(int64_t M, int K, int N) {
     // whole waves of resident workgroups: TI <= 3 -> 168 VGPRs, 3 per CU (768); TI 4,5 -> 2 per CU (512); TI 6 -> 1 per CU
     // stage 1 of a wide unit (5 or 6 column tiles: 225+ VGPRs, 1-2 workgroups per CU) runs as two column slices of <= 3 tiles
     // (168 VGPRs, 3 per CU): each slice streams its half of G and Y and all of the thin X
-    static const bool slicing = getenv("MNY_BNW_NOSLICE") == nullptr;
-    pl.nsl = (slicing && pl.TI >= 5) ? 2 : 1;
+    pl.nsl = pl.TI >= 5 ? 2 : 1;
     pl.TIs = (int)cdiv(pl.TI, pl.nsl);
     int64_t splits = (pl.TIs <= 3 ? 768 : 1024) / pl.nsl;
     const int64_t max_splits = cdiv(M, 64);
@@ -2852,14 +2678,14 @@ extern "C" int mny_pw_stat_parts(int64_t M, int K, int Nc) {
     if (M <= 0 || K <= 0 || Nc <= 0) return MNY_EINVAL;
     if (pw_thin_ok(0, 0, M, K, Nc)) return pw_thin_parts(M, K, Nc, 0);
     if (pw_wide_ok(M, K, Nc, false)) return pw_wide_parts(M, K, Nc, false) + ((M & 31) ? nt2_plan(M & 31, K, Nc, true).gx : 0);      // + the last M % 32 rows
-    if ((K & 3) == 0 && getenv("MNY_GEMM_V1") == nullptr) return nt2_plan(M, K, Nc, true).gx;
+    if ((K & 3) == 0 && !sw(SW_GEMM_V1)) return nt2_plan(M, K, Nc, true).gx;
     return nt_plan(M, K, Nc).gx;
 }
 extern "C" int mny_pw_stat_parts_bf16(int64_t M, int K, int Nc) {
     if (M <= 0 || K <= 0 || Nc <= 0) return MNY_EINVAL;
     if (pwt_ok(M, K, Nc, MNY_ACT_NONE, false)) return pwt_parts(M);
     if (pw_thin_ok(1, 0, M, K, Nc)) return pw_thin_parts(M, K, Nc, 0);
-    if ((K & 7) == 0 && getenv("MNY_GEMM_V1") == nullptr) return nt2_plan(M, K, Nc, true, 1).gx;
+    if ((K & 7) == 0 && !sw(SW_GEMM_V1)) return nt2_plan(M, K, Nc, true, 1).gx;
     return nt_plan(M, K, Nc).gx;
 }
 
@@ -2898,7 +2724,7 @@ extern "C" int mny_pw_fwd(const float* x, const float* in_scale, const float* in
     MNY_REQUIRE(!(stats && bias), "pw_fwd: stats and bias are mutually exclusive");
     hipStream_t st = (hipStream_t)stream;
     const bool xf = in_scale != nullptr || in_act != MNY_ACT_NONE;
-    static const bool force_v1 = getenv("MNY_GEMM_V1") != nullptr;   // A/B switch for profiling
+    const bool force_v1 = sw(SW_GEMM_V1);   // A/B switch for profiling
     if (pw_thin_ok(0, 0, M, K, Nc)) {                      // short reduction: vector-ALU stream kernel (pwthin.hip)
         g_pw_route = MNY_ROUTE_THIN;
         return pw_thin_launch(0, x, in_scale, in_shift, in_act, w, bias, addend, y, stats, M, K, Nc, 0, nullptr, nullptr, nullptr, nullptr, nullptr, 0, st);
@@ -2936,13 +2762,12 @@ extern "C" int mny_pw_fwd(const float* x, const float* in_scale, const float* in
 // transposed -> NT), and in the same epilogue that unit's BN-backward reduction over (dx, its raw output y): the separate
 // mny_bn_bwd_reduce pass (one more read of dx and of y) disappears — only y is read, by the tile that just produced dx.
 // the reduction epilogue holds four more per-column constants and a group of loads: the 160-column tile (TN = 5) spills with it
-static const int kRedMaxTn = getenv("MNY_RED_TN") ? atoi(getenv("MNY_RED_TN")) : 4;      // (A/B: 3 = no 128-column reduction tiles)
+constexpr int kRedMaxTn = 4;
 static bool dgrad_bnred_ok(int64_t M, int K, int Nc, int act) {
-    static const bool red512 = getenv("MNY_RED512") != nullptr && atoi(getenv("MNY_RED512")) != 0;
-    if (K >= 512 && Nc >= 512 && !red512) return false;      // matrix-pipe-bound: the reduce pass it would save is cheaper than the longer epilogue (MNY_RED512=1: A/B)
+    if (K >= 512 && Nc >= 512) return false;      // matrix-pipe-bound: the reduce pass it would save is cheaper than the longer epilogue
     if ((pw_thin_ok(0, 1, M, K, Nc) || pw_thin_ok(1, 1, M, K, Nc)) && act == MNY_ACT_HSIGMOID) return false;
     if (pw_wide_ok(M, K, Nc, true) && act >= MNY_ACT_HSWISH) return false;      // the wide-output kernel's reduction form knows the clamp family (its h-swish builds spill)      // the short-reduction kernel knows the clamp family and h-swish (what units use)
-    return M > 0 && K > 0 && Nc > 0 && (K & 3) == 0 && act >= MNY_ACT_NONE && act <= MNY_ACT_HSIGMOID && getenv("MNY_GEMM_V1") == nullptr;
+    return M > 0 && K > 0 && Nc > 0 && (K & 3) == 0 && act >= MNY_ACT_NONE && act <= MNY_ACT_HSIGMOID && !sw(SW_GEMM_V1);
 }
 extern "C" int mny_pw_dgrad_bnred_supported(int64_t M, int K, int Nc, int act) { return dgrad_bnred_ok(M, K, Nc, act) ? 1 : 0; }
 extern "C" int mny_pw_dgrad_bnred_parts(int64_t M, int K, int Nc) {
@@ -3041,8 +2866,7 @@ extern "C" int mny_pw_dgrad_bnred_bf16(const void* dy, const void* wT, void* dx,
 // BN-backward sums of the unit whose complete output gradient dx now is (its raw output ry, as mny_pw_dgrad_bnred_add).  Always the LDS-DMA
 // kernel, column tiles of <= 96 (the addend form's limit).
 static bool lr_fix_wide(int64_t M, int K, int r_act) {       // which kernel a call WITH a reduction target takes — the one rule for the launch and the row count
-    static const bool no_wide_fix = getenv("MNY_LR_FIX_DMA") != nullptr;          // (A/B: always the LDS-DMA kernel)
-    return !no_wide_fix && pw_wide_fix_ok(M, K) && r_act < MNY_ACT_HSWISH;
+    return pw_wide_fix_ok(M, K) && r_act < MNY_ACT_HSWISH;
 }
 static int pw_lr_fix_impl(const float* x, const float* in_scale, const float* in_shift, const float* q, const float* r, const float* addend, float* dx,
                           const float* ry, const float* r_scale, const float* r_shift, int r_act, const float* r_mean, const float* r_invstd, float* red,
@@ -3084,13 +2908,13 @@ extern "C" int mny_pw_lr_fix(const float* x, const float* in_scale, const float*
 // their third resident workgroup (7-18 % faster from ~60 FLOP per byte up, 10-30 % slower below ~40).  Round 3: the plane ring is two
 // slots deep (the A ring stays at three), the LDS footprint equals the plain mode's and the threshold moved down to 30 FLOP per byte.
 static bool w6_ok(int64_t M, int K, int Nc) {
-    static const bool off = getenv("MNY_NO_W6") != nullptr;
+    const bool off = sw(SW_NO_W6);
     // (round 3: with the two-slot plane ring the planes no longer cost a resident workgroup; same-box A/B per shape: K576 N96 -11 %,
     // K384 N96 -10 %, the 75-channel heads -9..-11 %, K384 N64 (27 FLOP per byte) +0..+7 % -> threshold 30, was 50)
-    static const double min_ai = getenv("MNY_W6_AI") ? atof(getenv("MNY_W6_AI")) : 30.0;
+    constexpr double min_ai = 30.0;
     const double ai = 2.0 * K * Nc / (4.0 * (K + Nc));
     return !off && M > 0 && K > 0 && Nc > 0 && (K & 3) == 0 && !pw_thin_ok(0, 0, M, K, Nc) && !pw_wide_ok(M, K, Nc, false) && !pw_wide_ok(M, K, Nc, true) && nt_x6(M, K, Nc) != 0 && ai >= min_ai &&
-           getenv("MNY_GEMM_V1") == nullptr;
+           !sw(SW_GEMM_V1);
 }
 extern "C" int mny_pw_w6_supported(int64_t M, int K, int Nc) { return w6_ok(M, K, Nc) ? 1 : 0; }
 extern "C" size_t mny_pw_w6_bytes(int K, int Nc) { return (K <= 0 || Nc <= 0) ? 0 : (size_t)3 * Nc * ((K + 15) / 16) * 32; }
@@ -3159,7 +2983,7 @@ extern "C" int mny_pw_fwd_bf16(const void* x, const float* in_scale, const float
     MNY_REQUIRE(!(stats && bias), "pw_fwd: stats and bias are mutually exclusive");
     hipStream_t st = (hipStream_t)stream;
     const bool xf = in_scale != nullptr || in_act != MNY_ACT_NONE;
-    static const bool force_v1 = getenv("MNY_GEMM_V1") != nullptr;
+    const bool force_v1 = sw(SW_GEMM_V1);
     // mny_pw_stat_parts_bf16 sizes the caller's partial rows from (M, K, Nc) alone: a view / bias that moves the call to another kernel family
     // than the query assumed would write a different number of rows than mny_bn_finalize sums — refuse it instead
     MNY_REQUIRE(!stats || pwt_ok(M, K, Nc, in_act, bias != nullptr) == pwt_ok(M, K, Nc, MNY_ACT_NONE, false),
@@ -3192,7 +3016,7 @@ extern "C" int mny_pw_last_route(void) { return g_pw_route; }
 // their order.  For shapes no plan at hand launches (tests ask it about the bs-256 shapes while running a bs-64 plan).
 extern "C" int mny_pw_route(int op, int bf16, int64_t M, int K, int Nc) {
     if (M <= 0 || K <= 0 || Nc <= 0 || op < 0 || op > 2) return MNY_EINVAL;
-    static const bool gemm_v1 = getenv("MNY_GEMM_V1") != nullptr, wgrad_v1 = getenv("MNY_WGRAD_V1") != nullptr;
+    const bool gemm_v1 = sw(SW_GEMM_V1), wgrad_v1 = sw(SW_WGRAD_V1);
     const int al = bf16 ? 7 : 3;
     if (op == 2) {
         if (!bf16 && pw_wgs_ok(M, K, Nc)) return MNY_ROUTE_WGRAD_STREAM;
@@ -3236,12 +3060,12 @@ static int pw_wgrad_impl(const T* x, const float* in_scale, const float* in_shif
         hipLaunchKernelGGL(reduce_parts_kernel, dim3((unsigned)cdiv(n, 32)), dim3(256), 0, (hipStream_t)stream, ws, pw_wgs_splits(M, K, Nc), n, dw);
         return check_launch("reduce_parts_kernel");
     }
-    static const bool force_v1 = getenv("MNY_WGRAD_V1") != nullptr;
+    const bool force_v1 = sw(SW_WGRAD_V1);
     const bool dma_f32 = is_f32 && (Nc & 3) == 0 && (K & 3) == 0 && in_act != MNY_ACT_HSWISH && !force_v1;
     WgPlan pl = wg_plan(M, K, Nc, !is_f32, dma_f32);
     WgradArgs a{x, in_scale, in_shift, in_act, dy, ws, M, K, Nc, pl.rows_per_block, 0, pl.gy, pl.splits};
     dim3 grid(pl.gx, pl.gy, pl.splits), block(256);
-    static const bool xcd_order = getenv("MNY_WGRAD_NO_XCD") == nullptr;      // (same-box A/B switch)
+    const bool xcd_order = !sw(SW_WGRAD_NO_XCD);      // (same-box A/B switch)
     WgradArgs a_dma = a;
     // (only with >= 64 splits, i.e. >= 8 per XCD: K1280 N512 — 40 tiles, 38 splits — lost 11 % to XCD imbalance)
     const bool use_xcd = xcd_order && pl.gx * pl.gy > 1 && pl.splits >= 64;
@@ -3368,13 +3192,12 @@ extern "C" size_t mny_pw_bnbwd_ws_floats(int64_t M, int K, int Nc) {
 }
 
 static bool bnw_red_ok(int64_t M, int K, int Nc) {      // the data-gradient stage that can carry the sums of the unit in front: the barrier-free second generation
-    static const int v2 = getenv("MNY_BND_V2") ? atoi(getenv("MNY_BND_V2")) : 1;
-    return bnw_supported(M, K, Nc) && v2 && (Nc == 96 || Nc == 144 || Nc == 192);
+    return bnw_supported(M, K, Nc) && (Nc == 96 || Nc == 144 || Nc == 192);
 }
+constexpr int kBndGrid = 512;      // workgroups of the barrier-free data-gradient stage: two per CU
 static int bnw_red_grid(int64_t M) {
-    static const int v2_grid = getenv("MNY_BND_V2_GRID") ? atoi(getenv("MNY_BND_V2_GRID")) : 512;
     const int64_t tiles = cdiv(M, 32);
-    return (int)(cdiv(tiles, 4) < v2_grid ? cdiv(tiles, 4) : v2_grid);
+    return (int)(cdiv(tiles, 4) < kBndGrid ? cdiv(tiles, 4) : kBndGrid);
 }
 static int pw_bnbwd_impl(const float* g, const float* y, const float* scale, const float* shift, int act,
                          const float* mean, const float* invstd, const float* gamma,
@@ -3402,31 +3225,13 @@ static int pw_bnbwd_impl(const float* g, const float* y, const float* scale, con
     const int64_t npairs = (M / 2 + 66) / 2 * 2;                      // even (16-B aligned rows of words) + a tile of slack
     BnwArgs a{g, y, scale, shift, act, mean, invstd, x, in_scale, in_shift, in_act, ws, mask, npairs, M, K, Nc, pl.rows_per_block, pl.TI};
     dim3 grid(pl.splits, pl.nsl), block(256);
-    if (!allow_lds((const void*)pw_bnbwd_stage1_kernel<5>, 96 * 1024) || !allow_lds((const void*)pw_bnbwd_stage1_kernel<6>, 96 * 1024)) {     // TI >= 5 needs more than 64 KB of dynamic LDS
-        set_error("pw_bnbwd: hipFuncSetAttribute failed"); return MNY_EHIP;
+    switch (pl.TIs) {                       // <= 4 column tiles per slice (bnw_plan): <= 54 KB of dynamic LDS
+        case 1: hipLaunchKernelGGL((pw_bnbwd_stage1b_kernel<1>), grid, block, pl.lds1, st, a); break;
+        case 2: hipLaunchKernelGGL((pw_bnbwd_stage1b_kernel<2>), grid, block, pl.lds1, st, a); break;
+        case 3: hipLaunchKernelGGL((pw_bnbwd_stage1b_kernel<3>), grid, block, pl.lds1, st, a); break;
+        default: hipLaunchKernelGGL((pw_bnbwd_stage1b_kernel<4>), grid, block, pl.lds1, st, a); break;
     }
-    static const bool s1v2 = getenv("MNY_BNW_S1V2") == nullptr || atoi(getenv("MNY_BNW_S1V2")) != 0;     // (=0: first-generation stage 1, A/B)
-    if (s1v2) {
-        if (!allow_lds((const void*)pw_bnbwd_stage1b_kernel<5>, 96 * 1024) || !allow_lds((const void*)pw_bnbwd_stage1b_kernel<6>, 96 * 1024)) {
-            set_error("pw_bnbwd: hipFuncSetAttribute failed"); return MNY_EHIP;
-        }
-        switch (pl.TIs) {
-            case 1: hipLaunchKernelGGL((pw_bnbwd_stage1b_kernel<1>), grid, block, pl.lds1, st, a); break;
-            case 2: hipLaunchKernelGGL((pw_bnbwd_stage1b_kernel<2>), grid, block, pl.lds1, st, a); break;
-            case 3: hipLaunchKernelGGL((pw_bnbwd_stage1b_kernel<3>), grid, block, pl.lds1, st, a); break;
-            case 4: hipLaunchKernelGGL((pw_bnbwd_stage1b_kernel<4>), grid, block, pl.lds1, st, a); break;
-            case 5: hipLaunchKernelGGL((pw_bnbwd_stage1b_kernel<5>), grid, block, pl.lds1, st, a); break;
-            default: hipLaunchKernelGGL((pw_bnbwd_stage1b_kernel<6>), grid, block, pl.lds1, st, a); break;
-        }
-    } else switch (pl.TIs) {
-        case 1: hipLaunchKernelGGL((pw_bnbwd_stage1_kernel<1>), grid, block, pl.lds1, st, a); break;
-        case 2: hipLaunchKernelGGL((pw_bnbwd_stage1_kernel<2>), grid, block, pl.lds1, st, a); break;
-        case 3: hipLaunchKernelGGL((pw_bnbwd_stage1_kernel<3>), grid, block, pl.lds1, st, a); break;
-        case 4: hipLaunchKernelGGL((pw_bnbwd_stage1_kernel<4>), grid, block, pl.lds1, st, a); break;
-        case 5: hipLaunchKernelGGL((pw_bnbwd_stage1_kernel<5>), grid, block, pl.lds1, st, a); break;
-        default: hipLaunchKernelGGL((pw_bnbwd_stage1_kernel<6>), grid, block, pl.lds1, st, a); break;
-    }
-    int rc = check_launch("pw_bnbwd_stage1_kernel");
+    int rc = check_launch("pw_bnbwd_stage1b_kernel");
     if (rc) return rc;
     hipLaunchKernelGGL(reduce_parts_kernel, dim3((unsigned)cdiv(stride, 32)), dim3(256), 0, st, ws, pl.splits, stride, red);
     hipLaunchKernelGGL(pw_bnbwd_finalize_kernel, dim3((unsigned)cdiv((int64_t)Nc * K, 256)), dim3(256), bnw_finalize_lds(Nc, K), st, red, w, gamma, mean, invstd,
@@ -3480,9 +3285,8 @@ extern "C" int mny_pw_bnbwd_red(const float* g, const float* y, const float* sca
 // Shapes: K in {8, 16, 24, 32}, N in {64, 72, 96, 144, 192} (the expand units of MobileNetV3 / MobileNetV2), M >= 4096.  Same three steps:
 // second-generation stage 1 on a bf16 LDS image, the fp32 finalize, the barrier-free data-gradient stage with widened 8-byte loads.
 static bool bnw_supported_bf16(int64_t M, int K, int N) {
-    // (stage 1 is instantiated for up to three column tiles per slice: with MNY_BNW_NOSLICE set the 144 / 192-column units would need
-    // five / six and every replay would fail — they are then not offered at all)
-    return bnw_supported(M, K, N) && (K & 7) == 0 && (N == 64 || N == 72 || N == 96 || N == 144 || N == 192) && bnw_plan(M, K, N).TIs <= 3;
+    // (stage 1 is instantiated for two and three column tiles per slice: 144 / 192 columns run as two slices of three)
+    return bnw_supported(M, K, N) && (K & 7) == 0 && (N == 64 || N == 72 || N == 96 || N == 144 || N == 192);
 }
 extern "C" int mny_pw_bnbwd_supported_bf16(int64_t M, int K, int Nc) { return bnw_supported_bf16(M, K, Nc) ? 1 : 0; }
 extern "C" int mny_pw_bnbwd_bf16(const void* g, const void* y, const float* scale, const float* shift, int act,
@@ -3511,17 +3315,14 @@ extern "C" int mny_pw_bnbwd_bf16(const void* g, const void* y, const float* scal
               pl.rows_per_block, pl.TI};
     dim3 grid(pl.splits, pl.nsl), block(256);
     // LDS: the bf16 ring is half the fp32 one, but the block reductions at the end use [3][16][64] + vector scratch in fp32
-    static const int deep = getenv("MNY_BNW_RING") ? atoi(getenv("MNY_BNW_RING")) : 3;       // stages of the bf16 ring: MNY_BNW_RING=6 measured round 5, same box: 15.24 / 15.24 vs 15.20 / 15.25 ms — no gain, 3 stays
-    const int S1 = deep == 3 ? 3 : 6;
+    constexpr int S1 = 3;       // stages of the bf16 ring
     size_t lds1 = (size_t)S1 * 16 * (2 * 32 * pl.TIs + 32) * sizeof(bf16_t);
     const size_t need = (size_t)4 * (2 * pl.TIs + 1) * 32 * sizeof(float);
     if (lds1 < need) lds1 = need;
     if (lds1 < 3 * 16 * 64 * sizeof(float)) lds1 = 3 * 16 * 64 * sizeof(float);
-    switch (pl.TIs * 10 + S1) {
-        case 23: hipLaunchKernelGGL((pw_bnbwd_stage1b_kernel<2, bf16_t, 3>), grid, block, lds1, st, a); break;
-        case 33: hipLaunchKernelGGL((pw_bnbwd_stage1b_kernel<3, bf16_t, 3>), grid, block, lds1, st, a); break;
-        case 26: hipLaunchKernelGGL((pw_bnbwd_stage1b_kernel<2, bf16_t, 6>), grid, block, lds1, st, a); break;
-        case 36: hipLaunchKernelGGL((pw_bnbwd_stage1b_kernel<3, bf16_t, 6>), grid, block, lds1, st, a); break;
+    switch (pl.TIs) {
+        case 2: hipLaunchKernelGGL((pw_bnbwd_stage1b_kernel<2, bf16_t, S1>), grid, block, lds1, st, a); break;
+        case 3: hipLaunchKernelGGL((pw_bnbwd_stage1b_kernel<3, bf16_t, S1>), grid, block, lds1, st, a); break;
         default: set_error("pw_bnbwd_bf16: no stage-1 kernel for %d column tiles", pl.TIs); return MNY_EUNSUPPORTED;
     }
     int rc = check_launch("pw_bnbwd_stage1b_kernel<bf16>");
@@ -3533,9 +3334,7 @@ extern "C" int mny_pw_bnbwd_bf16(const void* g, const void* y, const float* scal
     if (rc || !dx) return rc;
     BndArgs d{(const float*)g, mask, act, (const float*)x, in_scale, in_shift, in_act, B1, Q, bias, (const float*)addend, (float*)dx, npairs, M, Nc, K, pl.TI,
               pl.m_tiles, pl.tiles_per_block};
-    static const int v2_grid = getenv("MNY_BND_V2_GRID") ? atoi(getenv("MNY_BND_V2_GRID")) : 512;
-    const int64_t tiles = cdiv(M, 32);
-    const int grid2 = (int)(cdiv(tiles, 4) < v2_grid ? cdiv(tiles, 4) : v2_grid);
+    const int grid2 = bnw_red_grid(M);
     switch (Nc) {
         case 64: hipLaunchKernelGGL((pw_bnbwd_dgrad2_kernel<4, bf16_t, false>), dim3(grid2), dim3(256), 0, st, d); break;
         case 72: hipLaunchKernelGGL((pw_bnbwd_dgrad2_kernel<5, bf16_t, true>), dim3(grid2), dim3(256), 0, st, d); break;

@@ -264,8 +264,7 @@ struct ThinPlan { int nq, rpb, R, grid; int64_t ntiles; };
 //   bf16: half the bytes for the same instruction count, so the kernel is issue-bound near 3 TB/s: it wins where the bf16 MFMA
 //         k-step (32) is badly filled — K = 8 / 24, and the K = 16 data gradients — and loses at K = 32 and the K = 16 forward.
 bool pw_thin_ok(int bf, int red, int64_t M, int K, int N) {
-    static const bool off = getenv("MNY_NO_THIN") != nullptr;      // A/B switch
-    if (off) return false;
+    if (sw(SW_NO_THIN)) return false;      // A/B switch
     if (!(M > 0 && (K == 8 || K == 16 || K == 24 || K == 32) && (N & 3) == 0 && N >= 16 && N <= 256)) return false;
     if (bf) return K == 8 || K == 24 || (K == 16 && red);
     return true;
@@ -273,13 +272,12 @@ bool pw_thin_ok(int bf, int red, int64_t M, int K, int N) {
 
 // red != 0: the BN-backward epilogue's constants and prefetched rows push the K >= 16 variants past 168 VGPRs (two workgroups per CU)
 static ThinPlan thin_plan(int64_t M, int K, int N, int red) {
-    static const int res_env = getenv("MNY_THIN_RES") ? atoi(getenv("MNY_THIN_RES")) : 0;
     ThinPlan t;
     t.nq = N / 4;
     t.rpb = 256 / t.nq;
     t.R = kThinTileRows / t.rpb >= 8 ? 8 : 2;                      // the two instantiated row counts (N >= 64 : N < 64)
     t.ntiles = cdiv(M, (int64_t)t.R * t.rpb);
-    const int resident = res_env > 0 ? res_env : ((K <= 8 || (K <= 16 && !red)) ? 768 : 512);
+    const int resident = (K <= 8 || (K <= 16 && !red)) ? 768 : 512;
     t.grid = (int)(t.ntiles < resident ? t.ntiles : resident);
     return t;
 }

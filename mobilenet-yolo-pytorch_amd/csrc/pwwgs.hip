@@ -162,9 +162,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 struct WgsPlan { int TA, TB, slices_a, slices_b, splits, xcd_groups; int64_t rows_per_block; };
 
 bool pw_wgs_ok(int64_t M, int K, int N) {
-    static const bool off = getenv("MNY_NO_WGS") != nullptr || getenv("MNY_WGRAD_V1") != nullptr;
+    const bool off = sw(SW_NO_WGS) || sw(SW_WGRAD_V1);
     const int thin = K < N ? K : N, wide = K < N ? N : K;
-    static const int max_thin = getenv("MNY_WGS_MAXTHIN") ? atoi(getenv("MNY_WGS_MAXTHIN")) : 320;      // same-box A/B: 160 and 320 gain 20-25 %, 512 loses 5 %
+    constexpr int max_thin = 320;      // same-box A/B: 160 and 320 gain 20-25 %, 512 loses 5 %
     return !off && M >= 16384 && (M & 15) == 0 && thin >= 64 && thin <= max_thin && (thin & 31) == 0 && wide >= 2 * thin && (wide & 3) == 0;
 }
 
@@ -172,15 +172,13 @@ static WgsPlan wgs_plan(int64_t M, int K, int N) {
     WgsPlan pl;
     // slices of the wide side: 96 columns next to a 64-channel narrow side when they divide it (6 accumulator tiles either way; the cuts —
     // the vector-ALU cost — are shared by more matrix work: 5 cuts per 6 tiles instead of 4 per 4), else 64
-    static const int force_ws = getenv("MNY_WGS_SLICE") ? atoi(getenv("MNY_WGS_SLICE")) : 0;
     const int thin = K <= N ? K : N, wide = K <= N ? N : K;
     // a narrow side of more than 96 channels is taken in parts of 96 (the last one partly masked): 2-D tiling, both operands re-read from L2
     const int tblocks = thin / 32, tpart = tblocks <= 3 ? tblocks : ((tblocks % 2 == 0 && tblocks % 3 != 0) ? 2 : 3), tslices = (int)cdiv(tblocks, tpart);
-    int ws = (tpart == 2 && wide % 96 == 0) ? 3 : 2;
-    if (force_ws == 2 || (force_ws == 3 && tpart == 2)) ws = force_ws;
+    const int ws = (tpart == 2 && wide % 96 == 0) ? 3 : 2;
     if (K <= N) { pl.TB = tpart; pl.TA = ws; pl.slices_a = (int)cdiv(N, 32 * ws); pl.slices_b = tslices; }      // X narrow: slices of the dY columns
     else { pl.TA = tpart; pl.TB = ws; pl.slices_a = tslices; pl.slices_b = (int)cdiv(K, 32 * ws); }           // dY narrow: slices of the X columns
-    static const int blocks = getenv("MNY_WGS_BLOCKS") ? atoi(getenv("MNY_WGS_BLOCKS")) : 512;      // two workgroups per CU
+    constexpr int blocks = 512;      // two workgroups per CU
     const int slices = pl.slices_a * pl.slices_b;
     int64_t splits = blocks / slices;
     pl.xcd_groups = splits >= 32;                     // same-box A/B: with fewer row splits the grouping only costs parallelism (320->1280: 5 splits on 5 XCDs)

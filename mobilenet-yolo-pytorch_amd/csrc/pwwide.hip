@@ -290,24 +290,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 struct WidePlan { int KS, TNB, n_blocks, gx, grid; int64_t ntiles; size_t lds; };
 
 static bool wide_on() {
-    static const bool off = getenv("MNY_NO_WIDE") != nullptr || getenv("MNY_GEMM_V1") != nullptr;
-    return !off;
+    return !sw(SW_NO_WIDE) && !sw(SW_GEMM_V1);
 }
 
 static int wide_tnb(int /*K*/, int N, bool red) {     // column block = 32 * TNB columns, whole blocks only; 0 = no kernel
-    static const int force = getenv("MNY_WIDE_TNB") ? atoi(getenv("MNY_WIDE_TNB")) : 0;
     // (the reduction form takes blocks of at most 96 columns: its 128-column builds need scratch; every instantiation below is spill-free,
     // and tests/test_gpu_kernels.py pins run-to-run determinism of each one the nets use)
     const int cap = red ? 3 : 4;
-    if (force >= 2 && force <= cap && N % (32 * force) == 0) return force;
     if (N % 96 == 0 && cap >= 3) return 3;
     if (N % 128 == 0 && cap >= 4) return 4;
     return N % 64 == 0 ? 2 : 0;
 }
 
 bool pw_wide_ok(int64_t M, int K, int N, bool red) {
-    static const int min_ratio_x2 = getenv("MNY_WIDE_RATIO2") ? atoi(getenv("MNY_WIDE_RATIO2")) : 2;      // N >= ratio/2 * K
-    return wide_on() && M >= 8192 && K >= 52 && K <= 96 && (K & 3) == 0 && N >= 64 && wide_tnb(K, N, red) != 0 && 2 * (int64_t)N >= (int64_t)min_ratio_x2 * K;
+    return wide_on() && M >= 8192 && K >= 52 && K <= 96 && (K & 3) == 0 && N >= 64 && wide_tnb(K, N, red) != 0 && N >= K;
 }
 
 static WidePlan wide_plan(int64_t M, int K, int N, bool red) {
@@ -316,7 +312,7 @@ static WidePlan wide_plan(int64_t M, int K, int N, bool red) {
     pl.TNB = wide_tnb(K, N, red);
     pl.n_blocks = N / (32 * pl.TNB);
     pl.ntiles = M / 32;                                  // whole tiles; the last M % 32 rows go through the LDS-DMA kernel (one more partial row)
-    static const int res = getenv("MNY_WIDE_RES") ? atoi(getenv("MNY_WIDE_RES")) : 512;     // resident workgroups: 2 per CU
+    constexpr int res = 512;     // resident workgroups: 2 per CU
     int64_t gx = res / pl.n_blocks;
     if (gx >= 8) gx = gx / 8 * 8;                     // whole groups of 8 m-runs: every XCD gets the same number of workgroups (85 runs of 6 blocks
                                                       // put 66 on five XCDs with 64 slots each: K96 N576 0.131 -> 0.120 ms with 80 runs)

@@ -422,13 +422,11 @@ __global__ __launch_bounds__(256) void stem_wgrad_mfma_kernel(const float* __res
 }
 
 static bool stem_mfma_ok(int Cout) {
-    static const bool off = getenv("MNY_STEM_WGRAD_VALU") && getenv("MNY_STEM_WGRAD_VALU")[0] == '1';
-    return !off && (Cout == 16 || Cout == 32);
+    return !sw(SW_STEM_WGRAD_VALU) && (Cout == 16 || Cout == 32);
 }
 static int stem_mfma_grid(const StemGeom& g) {
-    static const int env = getenv("MNY_STEM_WG_GRID") ? atoi(getenv("MNY_STEM_WG_GRID")) : 0;
     const int64_t want = (int64_t)g.N * cdiv(g.Ho, ST_TH) * cdiv(g.Wo, ST_TW);
-    const int cap = env > 0 ? env : (g.Cout == 16 ? 768 : 512);      // 148-160 VGPRs at 16 channels (three resident workgroups per CU), 176-200 at 32 (two)
+    const int cap = g.Cout == 16 ? 768 : 512;      // 148-160 VGPRs at 16 channels (three resident workgroups per CU), 176-200 at 32 (two)
     return (int)(want < cap ? want : cap);
 }
 template <typename T, int REB>

@@ -339,7 +339,7 @@ static void sd_geom(SdGeom& g, int& gx, int N, int H, int W) {
 using namespace mny;
 
 extern "C" int mny_stemdw_supported(int N, int H, int W, int Cout, int s_act, int d_act) {
-    static const bool off = getenv("MNY_NO_STEMDW") != nullptr;
+    const bool off = sw(SW_NO_STEMDW);
     const bool acts = s_act != MNY_ACT_HSWISH && s_act != MNY_ACT_HSIGMOID && d_act != MNY_ACT_HSWISH && d_act != MNY_ACT_HSIGMOID;
     return (!off && acts && sd_shape_ok(N, H, W, Cout)) ? 1 : 0;
 }

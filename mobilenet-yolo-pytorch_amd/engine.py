@@ -19,7 +19,7 @@ import warnings
 
 import torch
 
-from . import _lib
+from . import _lib, switches
 from ._lib import ACT_NONE, MnyError, YoloHead
 
 _FWD_TICK = itertools.count()            # process-wide order of training forwards (NetPlan.last_fwd_tick)
@@ -226,6 +226,9 @@ class NetPlan:
         # (same arithmetic in fp32 registers, half the HBM bytes); weights, BN statistics, parameter gradients and the
         # detection heads seen by loss / decode stay fp32.
         assert act_dtype in (torch.float32, torch.bfloat16), act_dtype
+        # every switch the plan compiler knows (switches.py), read here, once per plan
+        sw_hipgraph, sw_side, sw_exdw_k, sw_no_gate = (switches.get(n) for n in ("MNY_HIPGRAPH", "MNY_SIDE_STREAM", "MNY_EXDW_K", "MNY_NO_GATE"))
+        self.sw_no_lr, self.sw_no_lr_s2, self.sw_no_dwfuse5s2 = (switches.get(n) for n in ("MNY_NO_LR", "MNY_NO_LR_S2", "MNY_NO_DWFUSE5S2"))
         self.adt = act_dtype
         self.bf16 = act_dtype == torch.bfloat16
         self.eb = 2 if self.bf16 else 4
@@ -240,19 +243,18 @@ class NetPlan:
         # optional hipGraph replay (MNY_HIPGRAPH=1): after two eager steps (which also run every one-time HIP attribute /
         # occupancy query) the call lists are captured once per segment and replayed.  Measured on MI355X: no gain
         # (68.1 vs 67.7 ms/step) — the eager list already keeps the GPU queue full — so it is off by default.
-        self.use_graphs = training and os.environ.get("MNY_HIPGRAPH", "0") == "1"
+        self.use_graphs = training and sw_hipgraph
         # weight-gradient kernels on a side stream: they feed nothing downstream in the backward pass, so they can overlap the
         # kernels of the following layers.  Fork = the side stream waits for what the main stream has enqueued (dY ready); join
         # before every batched combine and at the end of every replayed segment.  Measured (same-box A/B): no gain at
         # bs=256/352x352, where every kernel fills the chip (49.4 vs 49.5-49.8 ms), +3 % on MobileNetV3 512x512 bs=64 bf16, whose
         # 10-100 us kernels leave CUs idle (17.7 -> 17.2 ms).  Round 4 (same-box, un-bracketed steps): bs 256 / 352x352 38.19 -> 37.98 and
         # 38.07 -> 37.91 ms, so it is on up to 48 M input pixels; fewer resident depthwise-backward workgroups to make room for the side
-        # kernels lose more than the overlap gains (MNY_DWB_RES=512: +0.3 ms).  A step whose launches are bracketed with HIP events runs
+        # kernels lose more than the overlap gains (512 instead of 768: +0.3 ms).  A step whose launches are bracketed with HIP events runs
         # single-stream (the brackets must mean something): bench.py brackets every 4th timed step (--bracket-every), so three quarters of
         # the steps behind its `value` run with the side stream, one quarter without.  MNY_SIDE_STREAM=0/1 forces.
-        env_side = os.environ.get("MNY_SIDE_STREAM")
         auto_side = N * H * W <= 48 * 1000 * 1000
-        self.side_on = training and not self.use_graphs and (env_side == "1" or (env_side is None and auto_side))
+        self.side_on = training and not self.use_graphs and (sw_side == 1 or (sw_side is None and auto_side))
         self.stream_side = _vp(0)
         self._side_stream = torch.cuda.Stream(dev) if self.side_on else None
         self._ev_fork = torch.cuda.Event() if self.side_on else None
@@ -268,7 +270,6 @@ class NetPlan:
         self.eager_steps = 0
         self.x_static = None
         self.fwd = CallList()
-        self.cvt_batch = os.environ.get("MNY_NO_CBATCH") != "1"
         self._cvt_jobs = []
         self._cut_jobs = []           # (fp32 matrix, plane buffer): weights of the six-product GEMMs, cut once per pass (mny_cut3_batch)
         self.head32 = {}         # bf16 storage: value id -> fp32 copy of a detection head
@@ -301,7 +302,7 @@ class NetPlan:
         # from the thin input.  exdw_pw[expand node out id] = depthwise node, exdw_dw[depthwise node out id] = expand node.
         self.exdw_pw, self.exdw_dw = {}, {}
         if not self.bf16 and not self.frozen:           # (the frozen-BatchNorm backward runs on the generic, materialised kernels)
-            ks = set(int(v) for v in os.environ.get("MNY_EXDW_K", "16,24").split(",") if v)
+            ks = set(int(v) for v in sw_exdw_k.split(",") if v)
             cons = {}
             for nd in g.nodes:
                 for v in nd.ins:
@@ -322,7 +323,7 @@ class NetPlan:
         # (mobilenetv3.py:26-41,69-72).  gates[emit node out id] = dict(t, se0, se3, mul, add): the two hidden units are skipped where they stand
         # and the whole unit is emitted at the multiply (or, when the residual add is its only consumer, at the add, which it absorbs).
         self.gates, self.gate_units, self.gate_absorbed = {}, {}, set()
-        if self.bf16 and not self.frozen and os.environ.get("MNY_NO_GATE") != "1":
+        if self.bf16 and not self.frozen and not sw_no_gate:
             cons = {}
             for nd in g.nodes:
                 for v in nd.ins:
@@ -345,7 +346,7 @@ class NetPlan:
                             wq=torch.empty(int(_lib.query("mny_gate_wq_bytes", tv_.C, se0.out.C)), device=dev, dtype=torch.uint8))
                 emit_at = nd
                 mc = cons.get(nd.out.id, [])
-                if len(mc) == 1 and mc[0].op == "add" and mc[0].k == 1 and mc[0].ins[0] is nd.out and os.environ.get("MNY_GATE_NOADD") != "1":
+                if len(mc) == 1 and mc[0].op == "add" and mc[0].k == 1 and mc[0].ins[0] is nd.out:
                     gate["add"] = mc[0]                         # out = t * gate + view(other operand): the add node is absorbed
                     emit_at = mc[0]
                     self.gate_absorbed.add(nd.out.id)
@@ -363,51 +364,20 @@ class NetPlan:
                 continue
             live.add(v.id)
             stack.extend(v.node.ins)
-        self.dead_side = bool(self.side_on and bn_batch and os.environ.get("MNY_NO_DEAD_SIDE") != "1"
+        self.dead_side = bool(self.side_on and bn_batch
                               and any(nd.out.id not in live and nd.op in ("dw", "pw", "add") for nd in g.nodes))
         self.stats_ws_side = torch.empty(max_parts * 2 * maxC, **f32) if self.dead_side else self.stats_ws
         dead_forked = False
-        # A second forward LANE (round 6): the stride-16 neck / head chain (conv_for_S16, connect_for_S16, yolo_headS16: mbv2_yolo.py:146-153,
-        # mbv3_yolo.py:133-138) is independent of the stride-32 chain (features2 / bneck2, conv_for_S32, connect_for_S32, yolo_headS32) except for
-        # ONE edge (the upsampled stride-32 feature).  Every conv of a chain is followed by its BatchNorm finalize — a dependent ~6 us launch + the
-        # dispatch gap behind it — so two chains on two streams fill each other's bubbles.  Lane-2 nodes run on the second side stream with their own
-        # statistics workspace; a lane-2 node whose input was produced on the main stream since the last fork waits for it (fork2), the main stream
-        # waits for lane 2 before the losses (join2).  MEASURED SLOWER (same-box A/B, parity-green): headline 34.73 / 34.78 -> 34.78 / 34.89 ms,
-        # MobileNetV3 512x512 bf16 13.86 / 13.85 -> 13.99 / 14.02 ms — the two chains' kernels share the CUs and the cross-stream waits cost more than the
-        # finalize bubbles they fill.  OFF by default; MNY_LANE2=1 turns it on for A/B.
-        lane2_on = bool(self.side_on and bn_batch and os.environ.get("MNY_LANE2") == "1")
-        lane2_prefix = ("conv_for_S16", "connect_for_S16", "yolo_headS16")
-        self.stats_ws_lane2 = torch.empty(max_parts * 2 * maxC, **f32) if lane2_on else self.stats_ws
-        made = {}                     # value id -> (lane, index in the call list behind which it exists)
-        prev_node = None
-        last_fork2 = -1
-        lane2_used = False
         for nd in g.nodes:
             o = nd.out
             shp = shape(o)
             M = shp[0] * shp[1] * shp[2]
             dead = self.dead_side and o.id not in live and nd.op in ("dw", "pw", "add") and o.id not in self.exdw_pw and o.id not in self.exdw_dw
-            if prev_node is not None:
-                made[prev_node[0]] = (prev_node[1], len(self.fwd.calls))   # the previous node's value exists behind the calls appended so far
-            path = nd.conv or (nd.out.name if nd.op in ("add", "partadd") else "")
-            lane2 = (lane2_on and not dead and nd.op in ("dw", "pw", "pwb", "add", "partadd") and path.startswith(lane2_prefix)
-                     and o.id not in self.exdw_pw and o.id not in self.exdw_dw and o.id not in self.gates and o.id not in self.gate_units
-                     and o.id not in self.gate_absorbed)
-            st_n = self.stream_side if dead else (self.stream_side2 if lane2 else self.stream)          # the stream and statistics workspace of this node's calls
-            sws_n = self.stats_ws_side if dead else (self.stats_ws_lane2 if lane2 else self.stats_ws)
+            st_n = self.stream_side if dead else self.stream          # the stream and statistics workspace of this node's calls
+            sws_n = self.stats_ws_side if dead else self.stats_ws
             if dead and not dead_forked:
                 self.fwd.add_py(self._fork_side, "fork")                # the side stream waits for what the main stream has enqueued (the branch's input)
                 dead_forked = True
-            if lane2:
-                if any(made.get(v.id, (0, -1))[0] == 0 and made.get(v.id, (0, -1))[1] > last_fork2 for v in nd.ins) or not lane2_used:
-                    self.fwd.add_py(self._fork_side2, "fork")           # an input made on the main stream since the last fork: lane 2 waits for it
-                    last_fork2 = len(self.fwd.calls)
-                lane2_used = True
-            elif not dead and any(made.get(v.id, (0, -1))[0] == 2 for v in nd.ins):
-                self.fwd.add_py(self._join_side2, "join")               # (no graph of this package has such an edge; kept correct for any)
-                for k_ in [k_ for k_, mv in made.items() if mv[0] == 2]:
-                    made[k_] = (0, made[k_][1])
-            prev_node = (o.id, 2 if lane2 else (1 if dead else 0))
             if nd.op == "pw" and o.id in self.gate_units:
                 u = _Unit()                                   # a hidden unit of a gate: its BN coefficients live here, the calls come with the gate
                 u.Y = None                                    # never materialised
@@ -517,8 +487,6 @@ class NetPlan:
             else:
                 raise AssertionError(nd.op)
 
-        if lane2_used:
-            self.fwd.add_py(self._join_side2, "join")                   # both lanes meet before the losses / the decode
         self._flush_cvt_jobs()
         self._flush_cut_jobs(self.fwd, at_head=True)
         if self.gates:                                        # the gates' weights as matrix-core operand chunks, one launch per pass for all of them
@@ -596,10 +564,9 @@ class NetPlan:
                 ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
                 self.loss_ws.append(ws)
                 # the first head's loss (five short, latency-bound launches) runs on the side stream from the moment that head exists, next to the
-                # second head's branch (round 6; joined at the end of the list); MNY_NO_LOSS_SIDE=1: both losses at the end, on the main stream
+                # second head's branch (round 6; joined at the end of the list)
                 pos = next((k + 1 for k, c in enumerate(self.fwd.calls) if c is getattr(self, "_head0_call", None)), None)
-                early = (hi == 0 and self.side_on and self.bn_batch and pos is not None and pos < len(self.fwd.calls)
-                         and os.environ.get("MNY_NO_LOSS_SIDE") != "1")
+                early = (hi == 0 and self.side_on and self.bn_batch and pos is not None and pos < len(self.fwd.calls))
                 self.fwd.add("mny_yolo_loss", self.heads[hi], self.t_ptr, self.off_ptr, self.anchors[hi], self.masks[hi],
                              ctypes.byref(self.hp[hi]), self.out14[hi], self.dheads[hi], ws, self.stream_side if early else self.stream)
                 if early:
@@ -674,7 +641,7 @@ class NetPlan:
         # dW / pad entries of dbias land in slack reserved behind the parameter's gradient slot
         align = 8 if self.bf16 else 4
         self.head_cp = {nd.out.id: (nd.out.C + align - 1) // align * align for nd in order
-                        if nd.op == "pwb" and nd.out.C % align and os.environ.get("MNY_NO_HEADPAD") != "1"}
+                        if nd.op == "pwb" and nd.out.C % align}
         slack = {}
         for nd in order:
             if nd.out.id in self.head_cp:
@@ -722,9 +689,8 @@ class NetPlan:
         # Deferred partial combines: every weight-gradient call leaves per-workgroup partial sums; instead of one small combine
         # launch per layer (70 launches of 8-10 us at bs=256, 0.66 ms/step) the layer gets its OWN partial buffer, is called with
         # dw = NULL, and a whole run of layers is combined by one mny_reduce_batch launch (flush_reduce: every `defer_every` jobs, so
-        # the data-parallel buckets still complete early).  MNY_NO_DEFER=1: the per-layer combines.
-        self.defer = os.environ.get("MNY_NO_DEFER") != "1"
-        defer_every = int(os.environ.get("MNY_DEFER_EVERY", "16"))
+        # the data-parallel buckets still complete early).
+        defer_every = 16
         self._red_jobs, self._red_keep, self._post_reduce = [], [], []
         uses = {}
         for nd in order:                                          # a module applied twice (mbv3_yolo.py:133-134) adds a second contribution right
@@ -754,13 +720,11 @@ class NetPlan:
             # whose partial rows it reads (same stream = ordered) and, through the fork, behind everything the main stream has enqueued (the
             # fused units leave their partial rows there).  Every replayed segment ends with a join (run_bwd_segment), so gradients are
             # complete before an all-reduce or the optimizer sees them.  (Round 4 joined here and ran the combine on the main stream: 0.3 ms
-            # of 4-5 launches on the critical path of both benchmark configurations.)  MNY_REDUCE_MAIN=1: the round-4 placement.
-            if self.side_on and os.environ.get("MNY_REDUCE_MAIN") != "1":
+            # of 4-5 launches on the critical path of both benchmark configurations.)
+            if self.side_on:
                 bwd.add_py(self._fork_side, "fork")
                 red_stream = self.stream_side
             else:
-                if self.side_on:
-                    bwd.add_py(self._join_side, "join")           # the partials of side-stream weight gradients must have landed
                 red_stream = self.stream
             bwd.add("mny_reduce_batch", jdev, bdev, len(block_job), red_stream, meta=dict(writes=[job[1].data_ptr() for job in self._red_jobs]))
             for hook in self._post_reduce:                        # corrections of combined weight gradients (low-rank BN backward): same stream, right behind the combine
@@ -859,7 +823,7 @@ class NetPlan:
 
         def takes_own_sums(pn):
             """True for the thin expand units handled by mny_pw_bnbwd (their stage 1 forms the BN sums itself)."""
-            if pn.op != "pw" or self.frozen or os.environ.get("MNY_NO_BNFUSE") == "1" or (self.bf16 and os.environ.get("MNY_BNFUSE_BF16") == "0"):
+            if pn.op != "pw" or self.frozen:
                 return False                     # (frozen BatchNorm: that unit's own finalize assumes batch statistics)
             po, pi = pn.out, pn.ins[0]
             if pi.act in (_lib.ACT_HSWISH, _lib.ACT_HSIGMOID) or po.act in (_lib.ACT_HSWISH, _lib.ACT_HSIGMOID):
@@ -875,7 +839,7 @@ class NetPlan:
             t = None
             if i.kind == "unit":
                 t = i
-            elif i.node is not None and i.node.op == "add" and os.environ.get("MNY_NO_ADDRED") != "1":
+            elif i.node is not None and i.node.op == "add":
                 cands = [v for v in i.node.ins[:1 + (i.node.k & 1)] if v.kind == "unit" and n_consumers[v.id] == 1 and v.id not in loss_ids]
                 if len(cands) == 1:
                     t = cands[0]
@@ -889,8 +853,8 @@ class NetPlan:
         self.lr_units = set()
 
         def lr_ok(pn):
-            if (self.bf16 or self.frozen or not self.defer or pn.op != "pw" or pn.bias or not single(pn) or pn.out.id in self.head_cp
-                    or takes_own_sums(pn) or os.environ.get("MNY_NO_LR") == "1"):
+            if (self.bf16 or self.frozen or pn.op != "pw" or pn.bias or not single(pn) or pn.out.id in self.head_cp
+                    or takes_own_sums(pn) or self.sw_no_lr):
                 return False
             pi = pn.ins[0]
             if pi.act != ACT_NONE or pi.kind not in ("unit", "real"):
@@ -898,35 +862,33 @@ class NetPlan:
             psh = shape(pn.out)
             return _lib.query("mny_lr_supported", psh[0] * psh[1] * psh[2], pi.C, pn.out.C) == 1
         # W^T of every generic pointwise unit, all in one launch at the head of the backward list (one per layer was 39 launches)
-        self.t_batch = os.environ.get("MNY_NO_TBATCH") != "1"
-        if self.t_batch:
-            import numpy as np
-            jobs, block_job = [], []
+        import numpy as np
+        jobs, block_job = [], []
+        for nd in order:
+            if nd.op not in ("pw", "pwb") or takes_own_sums(nd) or nd.conv in self.wT:
+                continue
+            w = P[nd.conv + ".weight"]
+            oc = self.head_cp.get(nd.out.id, nd.out.C)
+            wT = torch.empty(nd.ins[0].C, oc, **act)
+            self.wT[nd.conv] = wT
+            nb = ((nd.ins[0].C + 31) // 32) * ((oc + 31) // 32)
+            jobs.append((w.data_ptr(), wT.data_ptr(), nd.out.C, nd.ins[0].C, oc, len(block_job)))
+            block_job += [len(jobs) - 1] * nb
+        if jobs:
+            jt = np.array(jobs, dtype=np.dtype([("src", np.uint64), ("dst", np.uint64), ("R", np.int32), ("Cc", np.int32), ("Rp", np.int32), ("b0", np.int32)]))
+            self.t_jobs = torch.from_numpy(jt.view(np.uint8).copy()).to(dev)
+            self.t_blocks = torch.tensor(block_job, dtype=torch.int32, device=dev)
+            bwd.add(K("mny_transpose_batch"), self.t_jobs, self.t_blocks, len(block_job), self.stream)
+            # ... and, for the data-gradient GEMMs that take the six-product bf16 form, the cut of W^T right behind it
+            self.wT6 = {}
             for nd in order:
-                if nd.op not in ("pw", "pwb") or takes_own_sums(nd) or nd.conv in self.wT:
-                    continue
-                w = P[nd.conv + ".weight"]
-                oc = self.head_cp.get(nd.out.id, nd.out.C)
-                wT = torch.empty(nd.ins[0].C, oc, **act)
-                self.wT[nd.conv] = wT
-                nb = ((nd.ins[0].C + 31) // 32) * ((oc + 31) // 32)
-                jobs.append((w.data_ptr(), wT.data_ptr(), nd.out.C, nd.ins[0].C, oc, len(block_job)))
-                block_job += [len(jobs) - 1] * nb
-            if jobs:
-                jt = np.array(jobs, dtype=np.dtype([("src", np.uint64), ("dst", np.uint64), ("R", np.int32), ("Cc", np.int32), ("Rp", np.int32), ("b0", np.int32)]))
-                self.t_jobs = torch.from_numpy(jt.view(np.uint8).copy()).to(dev)
-                self.t_blocks = torch.tensor(block_job, dtype=torch.int32, device=dev)
-                bwd.add(K("mny_transpose_batch"), self.t_jobs, self.t_blocks, len(block_job), self.stream)
-                # ... and, for the data-gradient GEMMs that take the six-product bf16 form, the cut of W^T right behind it
-                self.wT6 = {}
-                for nd in order:
-                    if nd.conv in self.wT and nd.conv not in self.wT6 and not takes_own_sums(nd):
-                        osh = shape(nd.out)
-                        oc = self.head_cp.get(nd.out.id, nd.out.C)
-                        pl6 = self._w6_planes(self.wT[nd.conv], osh[0] * osh[1] * osh[2], oc, nd.ins[0].C)
-                        if pl6 is not None:
-                            self.wT6[nd.conv] = pl6
-                self._flush_cut_jobs(bwd)
+                if nd.conv in self.wT and nd.conv not in self.wT6 and not takes_own_sums(nd):
+                    osh = shape(nd.out)
+                    oc = self.head_cp.get(nd.out.id, nd.out.C)
+                    pl6 = self._w6_planes(self.wT[nd.conv], osh[0] * osh[1] * osh[2], oc, nd.ins[0].C)
+                    if pl6 is not None:
+                        self.wT6[nd.conv] = pl6
+            self._flush_cut_jobs(bwd)
         for nd in order:
             o = nd.out
             shp = shape(o)
@@ -956,7 +918,7 @@ class NetPlan:
                         meta=dict(flops=4 * M * C * R, bytes=eb * 2 * M * C, shape="gate bwd1 M%d C%d R%d" % (M, C, R)))
                 bwd.add(fin_name, self.red_ws, gparts, M, P[se3.bn + ".weight"], u2.mean, u2.invstd, gv(se3.bn + ".weight"), gv(se3.bn + ".bias"), coef2, C, self.stream)
                 dw2 = gv(se3.conv + ".weight")
-                ws2 = defer_job(gparts * C * R, dw2, gparts, C * R)          # (always through the batched combine, MNY_NO_DEFER or not)
+                ws2 = defer_job(gparts * C * R, dw2, gparts, C * R)
                 bwd.add("mny_gate_bwd2_bf16", tv[0], tv[1], tv[2], G, wq, u1.scale, u1.shift, u1.mean, u1.invstd, u2.scale, u2.shift, coef2, self.red_ws, ws2,
                         M, C, R, self.stream, meta=dict(flops=8 * M * C * R, bytes=eb * 2 * M * C, shape="gate bwd2 M%d C%d R%d" % (M, C, R)))
                 bwd.add(fin_name, self.red_ws, gparts, M, P[se0.bn + ".weight"], u1.mean, u1.invstd, gv(se0.bn + ".weight"), gv(se0.bn + ".bias"), coef1, R, self.stream)
@@ -964,8 +926,7 @@ class NetPlan:
                 ws1 = defer_job(gparts * C * R, dw1, gparts, C * R)
                 rbuf = None
                 prod = t.node
-                if (_lib.query("mny_gate_bwd_red3_supported", C, R) == 1 and prod is not None and prod.op == "pw" and not takes_own_sums(prod)
-                        and os.environ.get("MNY_GATE_NORED3") != "1"):
+                if (_lib.query("mny_gate_bwd_red3_supported", C, R) == 1 and prod is not None and prod.op == "pw" and not takes_own_sums(prod)):
                     rbuf = torch.empty(gparts * 2 * C, **f32)        # dt is the project unit's complete output gradient: its BN-backward sums leave with it
                     self.fused_red[t.id] = (rbuf, gparts)
                 assert gs[t.id].buf is None, "the gate's input has another consumer"
@@ -994,7 +955,7 @@ class NetPlan:
                         self.coef_ws, o.C, self.stream)
                 dparts = _lib.query("mny_exdw_bwd_parts", N, psh[1], psh[2], pi.C, o.C, 2)
                 dwv = gv(nd.conv + ".weight")
-                if self.defer and single(nd):
+                if single(nd):
                     dwv_k, dws_k = None, defer_job(dparts * o.C * 9, dwv, dparts, o.C * 9)
                 else:
                     dwv_k, dws_k = dwv, torch.empty(dparts * o.C * 9, **f32)
@@ -1004,7 +965,7 @@ class NetPlan:
                 prod = pi.node
                 # the thin input is the raw output of a conv+BN unit consumed only here (the project conv in front of the first expand unit):
                 # the finished dX is that unit's complete output gradient -> its BN-backward sums leave with it, no separate reduce pass
-                if (os.environ.get("MNY_NO_EXRED") != "1" and pi.kind == "unit" and prod is not None and prod.op in ("pw", "dw", "stem") and gs[pi.id].buf is None
+                if (pi.kind == "unit" and prod is not None and prod.op in ("pw", "dw", "stem") and gs[pi.id].buf is None
                         and n_consumers[pi.id] == 1 and not takes_own_sums(prod) and xv[1] is not None and pi.act not in (_lib.ACT_HSWISH, _lib.ACT_HSIGMOID)
                         and _lib.query("mny_exdw_bwd_red_parts", N, psh[1], psh[2], pi.C, o.C, 2) > 0):
                     ppu = self.units[pi.id]
@@ -1086,7 +1047,7 @@ class NetPlan:
                 w = P[nd.conv + ".weight"]
                 # the data gradient of this unit completes the output gradient of the unit in front (the previous block's project conv, directly or
                 # through the residual add): that unit's BN-backward sums leave with stage 2 (round 6: mny_pw_bnbwd_red, fp32 storage)
-                tgt = red_target(i, nd) if (not self.bf16 and os.environ.get("MNY_NO_REDFUSE") != "1" and os.environ.get("MNY_NO_BNW_RED") != "1") else None
+                tgt = red_target(i, nd) if not self.bf16 else None
                 if tgt is not None and (tgt.act in (_lib.ACT_HSWISH, _lib.ACT_HSIGMOID) or _lib.query("mny_pw_bnbwd_red_supported", M, i.C, o.C) != 1):
                     tgt = None
                 if tgt is not None:
@@ -1121,7 +1082,7 @@ class NetPlan:
                 coef_u = torch.empty(3 * C, **f32)                 # private: the side-stream weight-gradient correction reads it long after coef_ws is reused
                 bwd.add(fin_name, red_buf, red_parts, M, P[nd.bn + ".weight"], u.mean, u.invstd, gv(nd.bn + ".weight"), gv(nd.bn + ".bias"), coef_u, C, self.stream)
                 bq, rb = torch.empty(Kc * Kc, **f32), torch.empty(Kc, **f32)
-                prep_side = self.side_on and os.environ.get("MNY_LR_PREP_MAIN") != "1"       # Q, r under the main-term GEMM below; joined in front of the correction
+                prep_side = self.side_on       # Q, r under the main-term GEMM below; joined in front of the correction
                 if prep_side:
                     bwd.add_py(self._fork_side2, "fork")
                 bwd.add("mny_lr_prep", coef_u, w, bq, rb, C, Kc, self.stream_side2 if prep_side else self.stream)
@@ -1148,7 +1109,7 @@ class NetPlan:
                 buf = gs[i.id].buf
                 if prep_side:
                     bwd.add_py(self._join_side2, "join")
-                tgt = red_target(i, nd) if os.environ.get("MNY_NO_REDFUSE") != "1" else None
+                tgt = red_target(i, nd)
                 if tgt is not None:
                     pu = self.units[tgt.id]
                     rparts = _lib.query("mny_pw_lr_fix_parts", M, Kc, tgt.act)
@@ -1169,7 +1130,7 @@ class NetPlan:
                 u = self.units[o.id]
                 parts = _lib.query("mny_bn_bwd_parts", M, o.C)
                 gam = P[nd.bn + ".weight"]
-                if (nd.op == "dw" and os.environ.get("MNY_NO_DWFUSE") != "1" and _lib.query("mny_dw_bnbwd_supported", nd.k, nd.stride) == 1
+                if (nd.op == "dw" and _lib.query("mny_dw_bnbwd_supported", nd.k, nd.stride) == 1
                         and o.act != _lib.ACT_HSIGMOID and nd.ins[0].act != _lib.ACT_HSIGMOID):
                     # 3x3 (register form) / 5x5 (tile form, csrc/dwtile.hip) stride-1 depthwise unit: dY is rebuilt on chip, one pass over
                     # (G, Y, X) yields dX and dW
@@ -1192,11 +1153,11 @@ class NetPlan:
                     # the input is the raw output of a conv+BN+act unit consumed ONLY here: this kernel's dX is that unit's complete
                     # output gradient, so it also leaves the unit's BN-backward sums (mny_dw_bnbwd_red) and the unit's separate
                     # bn_bwd_reduce pass — a re-read of dX and X — disappears (wide expand units, the stem, the neck's pointwise units)
-                    with_red = (os.environ.get("MNY_NO_DWRED") != "1" and i.kind == "unit" and prod is not None and prod.op in ("pw", "stem")
+                    with_red = (i.kind == "unit" and prod is not None and prod.op in ("pw", "stem")
                                 and gs[i.id].buf is None and n_consumers[i.id] == 1 and not takes_own_sums(prod) and xv[1] is not None
                                 and i.act not in (_lib.ACT_HSIGMOID,))
                     pflags = (1 if self.bf16 else 0) | (2 if with_red else 0)        # (the row count depends on the form that runs: csrc/dwtile.hip dwt_use)
-                    if self.defer and single(nd):
+                    if single(nd):
                         dparts = _lib.query("mny_dw_bnbwd_parts_k", N, ish[1], ish[2], o.C, nd.k, pflags)
                         dwv_k, ws_k = None, defer_job(dparts * o.C * kk, dwv, dparts, o.C * kk)
                     # stem -> this depthwise unit (MobileNetV2's first two units): ONE pass yields both units' parameter gradients; the stem's
@@ -1207,11 +1168,8 @@ class NetPlan:
                         pu = self.units[i.id]
                         sparts = _lib.query("mny_stemdw_bwd_parts", N, self.H, self.W, i.C)
                         xws = torch.empty(max(int(_lib.query("mny_stemdw_bwd_ws_floats", N, self.H, self.W, i.C)), 4), **f32)
-                        if self.defer:
-                            self._red_jobs.pop()            # the job registered above counts the rows of mny_dw_bnbwd's partial buffer
-                            dwv_k, ws_k = None, defer_job(sparts * o.C * 9, dwv, sparts, o.C * 9)
-                        else:
-                            dwv_k, ws_k = dwv, torch.empty(sparts * o.C * 9, **f32)
+                        self._red_jobs.pop()            # the job registered above counts the rows of mny_dw_bnbwd's partial buffer
+                        dwv_k, ws_k = None, defer_job(sparts * o.C * 9, dwv, sparts, o.C * 9)
                         bwd.add("mny_stemdw_bwd", G, u.Y, u.scale, u.shift, o.act, self.coef_ws, pu.Y, pu.scale, pu.shift, pu.mean, pu.invstd,
                                 P[prod.bn + ".weight"], i.act, self.x_ptr, P[prod.conv + ".weight"], wt,
                                 gv(prod.conv + ".weight"), gv(prod.bn + ".weight"), gv(prod.bn + ".bias"), dwv_k, ws_k, xws,
@@ -1245,7 +1203,7 @@ class NetPlan:
                     flush_reduce()
                     bwd.marks[o.name] = len(bwd.calls)
                     continue
-                if (nd.op == "dw" and nd.k == 3 and nd.stride == 2 and os.environ.get("MNY_NO_DWFUSE2") != "1"
+                if (nd.op == "dw" and nd.k == 3 and nd.stride == 2
                         and o.act != _lib.ACT_HSIGMOID and nd.ins[0].act != _lib.ACT_HSIGMOID):
                     # 3x3 stride-2 depthwise unit: the same fusion (mny_dw_bnbwd_s2): no dY tensor, one launch instead of three
                     i = nd.ins[0]
@@ -1261,13 +1219,13 @@ class NetPlan:
                     dwv = gv(nd.conv + ".weight")
                     wt = P[nd.conv + ".weight"]
                     dwv_k, ws_k = dwv, self.ws
-                    if self.defer and single(nd):
+                    if single(nd):
                         dparts = _lib.query("mny_dw_bnbwd_s2_parts", N, ish[1], ish[2], o.C)
                         dwv_k, ws_k = None, defer_job(dparts * o.C * 9, dwv, dparts, o.C * 9)
                     prod = i.node
                     # behind a wide expand unit on the low-rank BN backward (round 6): the producer's sums and  ca o dX o relu6'(z)  leave with this pass
                     if (not self.bf16 and i.kind == "unit" and prod is not None and prod.op == "pw" and gs[i.id].buf is None and n_consumers[i.id] == 1
-                            and xv[1] is not None and i.act == _lib.ACT_RELU6 and lr_ok(prod) and os.environ.get("MNY_NO_LR_S2") != "1"):
+                            and xv[1] is not None and i.act == _lib.ACT_RELU6 and lr_ok(prod) and not self.sw_no_lr_s2):
                         pu = self.units[i.id]
                         rparts = _lib.query("mny_dw_bnbwd_s2_parts", N, ish[1], ish[2], o.C)
                         rbuf = torch.empty(rparts * 2 * i.C, **f32)
@@ -1289,7 +1247,7 @@ class NetPlan:
                     flush_reduce()
                     bwd.marks[o.name] = len(bwd.calls)
                     continue
-                if (nd.op == "dw" and nd.k == 5 and nd.stride == 2 and os.environ.get("MNY_NO_DWFUSE5S2") != "1" and o.C % 2 == 0
+                if (nd.op == "dw" and nd.k == 5 and nd.stride == 2 and not self.sw_no_dwfuse5s2 and o.C % 2 == 0
                         and o.act != _lib.ACT_HSIGMOID and nd.ins[0].act != _lib.ACT_HSIGMOID):
                     # 5x5 stride-2 depthwise unit (MobileNetV3's two down-sampling 5x5 blocks): mny_dw_bnbwd_s2k5 — one launch instead of
                     # bn_bwd_apply + dw5_wgrad + dw_bwd_data_s2k5, and the producer's BN-backward sums with it where the unit is its only consumer
@@ -1307,10 +1265,10 @@ class NetPlan:
                     wt = P[nd.conv + ".weight"]
                     dparts = _lib.query("mny_dw_bnbwd_s2k5_parts", N, ish[1], ish[2], o.C)
                     dwv_k, ws_k = dwv, self.ws
-                    if self.defer and single(nd):
+                    if single(nd):
                         dwv_k, ws_k = None, defer_job(dparts * o.C * 25, dwv, dparts, o.C * 25)
                     prod = i.node
-                    with_red = (os.environ.get("MNY_NO_DWRED") != "1" and i.kind == "unit" and prod is not None and prod.op in ("pw", "stem")
+                    with_red = (i.kind == "unit" and prod is not None and prod.op in ("pw", "stem")
                                 and gs[i.id].buf is None and n_consumers[i.id] == 1 and not takes_own_sums(prod) and xv[1] is not None
                                 and i.act not in (_lib.ACT_HSIGMOID,))
                     pu, rbuf = None, None
@@ -1350,10 +1308,7 @@ class NetPlan:
                         rbuf = torch.empty(rparts * 2 * i.C, **f32)
                         self.fused_red[i.id] = (rbuf, rparts)
                         dwv = gv(nd.conv + ".weight")
-                        if self.defer:
-                            dwv_k, ws_k = None, defer_job(rparts * o.C * i.C, dwv, rparts, o.C * i.C)
-                        else:
-                            dwv_k, ws_k = dwv, torch.empty(rparts * o.C * i.C, **f32)
+                        dwv_k, ws_k = None, defer_job(rparts * o.C * i.C, dwv, rparts, o.C * i.C)
                         contribute_kernel(i, lambda out, addend, G=G, u=u, pu=pu, w=P[nd.conv + ".weight"], dwv=dwv_k, wsl=ws_k, rbuf=rbuf, M=M, Ki=i.C, No=o.C, act_=i.act: bwd.add(
                             self.K("mny_pj_bwd"), G, u.Y, self.coef_ws, pu.Y, pu.scale, pu.shift, pu.mean, pu.invstd, act_, w, out, dwv, wsl, rbuf, M, Ki, No, self.stream,
                             meta=dict(flops=4 * M * Ki * No, bytes=self.eb * (2 * M * No + 2 * M * Ki), shape="project M%d K%d N%d" % (M, Ki, No))))
@@ -1361,7 +1316,7 @@ class NetPlan:
                         flush_reduce()
                         bwd.marks[o.name] = len(bwd.calls)
                         continue
-                stem_fused = (nd.op == "stem" and os.environ.get("MNY_NO_STEMFUSE") != "1" and _lib.query("mny_stem_bnwgrad_supported", o.C) == 1)
+                stem_fused = (nd.op == "stem" and _lib.query("mny_stem_bnwgrad_supported", o.C) == 1)
                 if not stem_fused:
                     bwd.add(K("mny_bn_bwd_apply"), G, u.Y, u.scale, u.shift, o.act, self.coef_ws, dY, M, o.C, self.stream,
                             meta=dict(flops=0, bytes=3 * eb * M * o.C, shape="M%d C%d" % (M, o.C)))
@@ -1369,7 +1324,7 @@ class NetPlan:
             if nd.op == "stem" and stem_fused:
                 # the stem has no data gradient: its only consumer of dY is the weight gradient, which rebuilds dY from (G, Y) on load
                 sdw, sws = gv(nd.conv + ".weight"), self.ws
-                if self.defer and single(nd):
+                if single(nd):
                     sparts = _lib.query("mny_stem_wgrad_parts", N, self.H, self.W, o.C)
                     sdw, sws = None, defer_job(sparts * o.C * 27, sdw, sparts, o.C * 27)
                 bwd.add(K("mny_stem_bnwgrad"), self.x_ptr, G, u.Y, u.scale, u.shift, o.act, self.coef_ws, sdw, sws,
@@ -1389,7 +1344,7 @@ class NetPlan:
                 if on_side:
                     bwd.add_py(self._fork_side, "fork")
                 dws_ = self.ws_side if on_side else self.ws
-                if self.defer and single(nd):
+                if single(nd):
                     wparts = _lib.query("mny_dw_wgrad_parts", N, ish[1], ish[2], o.C, nd.k, nd.stride)
                     dws_, dwv_ = defer_job(wparts * o.C * nd.k * nd.k, dwv_, wparts, o.C * nd.k * nd.k), None
                 bwd.add(K("mny_dw_bwd_weight"), xv[0], xv[1], xv[2], xv[3], dY, dwv_, dws_, N, ish[1], ish[2], o.C,
@@ -1408,28 +1363,19 @@ class NetPlan:
                 if on_side:
                     bwd.add_py(self._fork_side, "fork")
                 pws_ = self.ws_side if on_side else self.ws
-                if self.defer and db is None and single(nd):
+                if db is None and single(nd):
                     psplits = _lib.query(K("mny_pw_wgrad_splits"), M, i.C, oc)
                     pws_, dwv_ = defer_job(max(_lib.query("mny_pw_wgrad_ws_floats", M, i.C, oc), psplits * oc * i.C), dwv_, psplits, oc * i.C), None
                 bwd.add(K("mny_pw_wgrad"), xv[0], xv[1], xv[2], xv[3], dY, dwv_, db, pws_, M, i.C, oc,
                         self.stream_side if on_side else self.stream,
                         meta=dict(flops=2 * M * i.C * o.C, bytes=eb * (M * i.C + M * o.C) + 4 * i.C * o.C, shape="M%d K%d N%d" % (M, i.C, oc)))
-                if self.t_batch:
-                    wT = self.wT[nd.conv]               # filled by the batched transpose at the head of the list
-                else:
-                    wT = torch.empty(i.C, oc, **act)    # the data-gradient GEMM reads W^T in the activation storage type
-                    self.wT[nd.conv] = wT
-                    if oc != o.C:
-                        bwd.add(K("mny_transpose_pad"), w, wT, o.C, i.C, oc, self.stream)
-                    else:
-                        bwd.add(K("mny_transpose"), w, wT, o.C, i.C, self.stream)
+                wT = self.wT[nd.conv]                   # filled by the batched transpose at the head of the list
                 prod = i.node
                 wT6 = getattr(self, "wT6", {}).get(nd.conv)      # pre-cut W^T planes: this data gradient takes the six-product bf16 form
                 # (bf16 storage: round 2 measured the epilogue's 2-byte loads of the unit's output at what the saved pass cost, 3 281 vs
-                # 3 293 img/s on MobileNetV3 512; with round 3's kernels it wins — same-box A/B 17.65-17.70 vs 17.93-17.99 ms/step — and is on;
-                # MNY_REDFUSE_BF16=0 turns it off for A/B)
+                # 3 293 img/s on MobileNetV3 512; with round 3's kernels it wins — same-box A/B 17.65-17.70 vs 17.93-17.99 ms/step — and is on)
                 # the unit whose complete output gradient this data gradient is (i itself, or — through a residual add — the add's unit operand)
-                tgt = red_target(i, nd) if (os.environ.get("MNY_NO_REDFUSE") != "1" and (not self.bf16 or os.environ.get("MNY_REDFUSE_BF16") != "0")) else None
+                tgt = red_target(i, nd)
                 if (tgt is not None and gs[i.id].buf is None
                         and _lib.query(K("mny_pw_dgrad_bnred_supported"), M, oc, i.C, tgt.act) == 1):
                     # this data gradient IS the complete dL/d(output) of a conv+BN+act unit whose backward starts with a BN reduction:
@@ -1447,7 +1393,7 @@ class NetPlan:
                         contribute_kernel(i, lambda out, addend, dY=dY, wT=wT, M=M, K=oc, Nc=i.C, pu=pu, rbuf=rbuf, act_=tgt.act: bwd.add(
                             self.K("mny_pw_dgrad_bnred"), dY, wT, out, pu.Y, pu.scale, pu.shift, act_, pu.mean, pu.invstd, rbuf, M, K, Nc, self.stream,
                             meta=dict(flops=2 * M * K * Nc, bytes=self.eb * (M * K + 2 * M * Nc) + 4 * K * Nc, shape="dgrad+red M%d K%d N%d" % (M, K, Nc))))
-                elif (tgt is not None and os.environ.get("MNY_NO_REDADD") != "1" and gs[i.id].buf is not None
+                elif (tgt is not None and gs[i.id].buf is not None
                         and _lib.query(K("mny_pw_dgrad_bnred_add_supported"), M, oc, i.C, tgt.act) == 1):
                     # the LAST contribution to the output gradient of a conv+BN+act unit (a project conv feeding a residual add and the
                     # next block — or the block input that IS that residual sum): the earlier contributions arrive as the addend, the epilogue
@@ -1508,10 +1454,7 @@ class NetPlan:
         if not self.bf16:
             return w
         w16 = torch.empty(w.shape, device=self.dev, dtype=torch.bfloat16)
-        if self.cvt_batch:
-            self._cvt_jobs.append((w, w16))          # one batched conversion at the head of the forward list (_flush_cvt_jobs)
-        else:
-            self.fwd.add("mny_cvt_f32_bf16", w, w16, w.numel(), self.stream)
+        self._cvt_jobs.append((w, w16))              # one batched conversion at the head of the forward list (_flush_cvt_jobs)
         return w16
 
     def _flush_cvt_jobs(self):

@@ -65,3 +65,109 @@ def test_product_has_no_oracle_import():
             if f.endswith((".py", ".hip", ".h")):
                 txt = open(os.path.join(root, f)).read()
                 assert "import oracle" not in txt and "from oracle" not in txt, f
+
+
+PKG = os.path.join(REPO, "mobilenet-yolo-pytorch_amd")
+_NAME = re.compile(r"MNY_[A-Z0-9_]+")
+
+
+def _pkg_sources(exts):
+    for root, _, files in os.walk(PKG):
+        for f in sorted(files):
+            if f.endswith(exts):
+                yield os.path.relpath(os.path.join(root, f), PKG), open(os.path.join(root, f)).read()
+
+
+def _c_table():
+    """rows of MNY_SWITCHES in csrc/common.h -> {id: (name, type, default)}"""
+    src = open(os.path.join(PKG, "csrc", "common.h")).read()
+    rows = re.findall(r'^\s*X\((\w+), "(MNY_[A-Z0-9_]+)", (k\w+), (-?\d+), ([01]), "[^"]+"\)', src, flags=re.M)
+    return {r[0]: (r[1], r[2], int(r[3])) for r in rows}
+
+
+def test_switch_table_matches_the_code():
+    """One table of MNY_* switches: every name read anywhere in the package is a row, every row is read somewhere, the C rows and the
+    Python rows agree, and the environment is only reached through the two accessors (mny::sw in core.hip, switches.get)."""
+    from mobilenet_yolo_pytorch_amd import switches
+    table = {row[0]: row for row in switches.TABLE}
+    assert len(table) == len(switches.TABLE)
+    ctab = _c_table()
+    assert len(ctab) >= 15 and len({v[0] for v in ctab.values()}) == len(ctab)
+    # C side: getenv only inside the accessor, never with a literal name; every sw(SW_x) names a row, every row is used
+    used_c = set()
+    for rel, txt in _pkg_sources((".hip", ".h")):
+        assert 'getenv("MNY_' not in txt, rel
+        if rel != os.path.join("csrc", "core.hip"):
+            assert "getenv" not in re.sub(r"//[^\n]*", "", txt), rel + ": getenv outside the accessor of core.hip"
+        used_c |= set(re.findall(r"\bsw\(SW_(\w+)\)", txt))
+    core = open(os.path.join(PKG, "csrc", "core.hip")).read()
+    assert len(re.findall(r"\bgetenv\(", core)) == 1 and "getenv(s.name)" in core
+    assert used_c == set(ctab), (used_c ^ set(ctab))
+    # Python side: os.environ only inside switches.py (build.py reads HIPCC, no switch); every switches.get("...") names a row
+    used_py = set()
+    for rel, txt in _pkg_sources((".py",)):
+        if rel != "switches.py":
+            assert not _NAME.search(" ".join(re.findall(r"[^\n]*environ[^\n]*", txt))), rel + ": MNY_* read outside switches.get"
+            assert "getenv" not in txt, rel
+        used_py |= set(re.findall(r'switches\.get\(\s*"(MNY_[A-Z0-9_]+)"', txt))
+        for names in re.findall(r"switches\.get\(n\) for n in \(([^)]*)\)", txt):
+            used_py |= set(_NAME.findall(names))
+    assert used_py <= set(table), used_py - set(table)
+    c_names = {v[0] for v in ctab.values()}
+    assert c_names <= set(table), c_names - set(table)
+    kinds = {"kFlag": switches.FLAG, "kInt": switches.INT, "kWord": switches.WORD}
+    for name, kind, default in ctab.values():
+        assert table[name][1] == kinds[kind] and table[name][2] == default and "lib" in table[name][3].split(), name
+    # both directions: a row is read by the library, by the package's Python, or is one of bench.py's own
+    for name, row in table.items():
+        readers = set(row[3].split())
+        assert readers <= {"lib", "plan", "loader", "bench"} and readers, name
+        assert ("lib" in readers) == (name in c_names), name
+        assert bool(readers & {"plan", "loader"}) == (name in used_py), name
+    bench = set(_NAME.findall(" ".join(re.findall(r"[^\n]*environ[^\n]*|[^\n]*env\[[^\n]*", open(os.path.join(REPO, "bench.py")).read()))))
+    assert {n for n, row in table.items() if row[3] == "bench"} <= bench
+
+
+def test_tests_and_bench_only_use_live_switches():
+    """Every MNY_* environment variable that a test or bench.py reads or sets is a row of the table."""
+    from mobilenet_yolo_pytorch_amd import switches
+    table = {row[0] for row in switches.TABLE}
+    not_switches = {"MNY_ROUTE_WAVE16", "MNY_E", "MNY_OK", "MNY_EINVAL", "MNY_EHIP", "MNY_EUNSUPPORTED", "MNY_LGKM_WAIT", "MNY_SWITCHES"}
+    files = [os.path.join(REPO, "bench.py")] + [os.path.join(REPO, "tests", f) for f in sorted(os.listdir(os.path.join(REPO, "tests"))) if f.endswith(".py")]
+    for path in files:
+        names = {n for n in _NAME.findall(open(path).read()) if not n.startswith(("MNY_ACT_", "MNY_ROUTE_"))} - not_switches
+        assert names <= table, (os.path.basename(path), sorted(names - table))
+
+
+def test_unknown_switch_warns_once_by_name(monkeypatch):
+    from mobilenet_yolo_pytorch_amd import switches
+    retired = "MNY_" + "NO_TBATCH"
+    monkeypatch.setenv(retired, "1")
+    with pytest.warns(RuntimeWarning, match=retired) as rec:
+        switches.warn_unknown()
+    assert len([w for w in rec if retired in str(w.message)]) == 1
+    with pytest.raises(KeyError):
+        switches.get(retired)
+
+
+# what the toolchain leaves in the dynamic table besides the C ABI, by type and prefix: the host-side kernel handle objects (one data symbol per
+# __global__ function, `D`, or per instantiation of a __global__ template, weak `V`; hipLaunchKernel takes their address), weak libstdc++
+# instantiations (std::map / std::mutex of core.hip and pwgemm.hip), and the HIP compilation-unit ids
+_KERNEL_HANDLE = re.compile(r"_Z(N3mny)?\d+[a-z0-9_]*_kernel")
+_ALLOWED_PREFIX = {"W": ("_ZNSt", "_ZSt", "_ZNKSt"), "V": ("_ZNSt", "_ZSt", "_ZTSSt", "_ZTISt", "_ZTVSt"), "B": ("__hip_cuid_",), "D": ("__hip_cuid_",)}
+
+
+def test_only_the_c_abi_is_exported(lib_path):
+    import subprocess
+    out = subprocess.run(["nm", "-D", "--defined-only", lib_path], capture_output=True, text=True, check=True).stdout
+    syms = [ln.split()[-2:] for ln in out.splitlines() if len(ln.split()) >= 2]
+    assert len(syms) > 100
+    declared = set(_declared()) | {"_init", "_fini"}
+    text = [n for t, n in syms if t in "Tt"]
+    assert sorted(set(text) - {"_init", "_fini"}) == sorted(declared - {"_init", "_fini"}), sorted(set(text) ^ declared)
+    assert not [n for t, n in syms if "__device_stub__" in n]
+    assert not [n for t, n in syms if t in "TtW" and re.match(r"_ZN?K?3mny", n)], "namespace mny leaks text symbols"
+    for t, n in syms:
+        if t in "Tt":
+            continue
+        assert (t in "DV" and _KERNEL_HANDLE.match(n)) or n.startswith(_ALLOWED_PREFIX.get(t, ())), (t, n)

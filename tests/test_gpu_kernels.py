@@ -532,8 +532,8 @@ def test_fused_dw_unit_backward_with_producer_bn_sums(ops, N, H, W, C, act, xact
                                            (2, 11, 11, 960, 1, 1), (3, 33, 17, 32, 1, 2), (1, 7, 50, 200, 2, 0), (2, 37, 5, 64, 1, 4), (2, 3, 3, 32, 2, 3),
                                            (1, 1, 9, 16, 1, 1), (2, 9, 1, 16, 2, 2)])
 def test_dw_forward_odd_shapes_and_views(ops, N, H, W, C, s, act, monkeypatch):
-    """Both generations of the 3x3 depthwise forward (MNY_DW_V1=1 selects the sliding-window kernel the 5x5 layers still use; the
-    switch is read once per process, so this checks whichever one the process started with, on shapes with odd sizes, one-pixel
+    """Both generations of the 3x3 depthwise forward (MNY_DW_V1=1 selects the first-generation sliding-window kernel; like every
+    switch of the library it is read once per process, so this checks whichever one the process started with, on shapes with odd sizes, one-pixel
     images and every view activation): same outputs and BN partial sums as torch, 1e-4."""
     x = rnd(N, C, H, W, seed=1)
     w = rnd(C, 1, 3, 3, seed=2, scale=0.4)

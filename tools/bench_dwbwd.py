@@ -1,6 +1,5 @@
 #!/usr/bin/env python3
-"""Timing of the fused depthwise 3x3 stride-1 backward (csrc/dwbwd.hip) at the shapes of the bs-256 / 352x352 plan.  The knobs of
-that file (MNY_DWB_TH, MNY_DWB_RES, MNY_DWB_XCD, MNY_STENCIL_CGB) are read once per process, so run it once per setting:
+"""Timing of the fused depthwise 3x3 stride-1 backward (csrc/dwbwd.hip) at the shapes of the bs-256 / 352x352 plan:
     python tools/bench_dwbwd.py [bs] [f32|bf16] [K]   prints ms, algorithmic GB/s and fp64 checksums of dX / dW / producer sums per shape
 bf16: the shapes of the MobileNetV3-YOLO 512x512 bs-64 plan.  K = 5: the 5x5 stride-1 units of that plan (tile form, csrc/dwtile.hip) next to
 the launches they replace (bn_bwd_apply + dw_bwd_weight + dw_bwd_data + the producer's bn_bwd_reduce); K = 3 with MNY_DWT3=1: the tile form on 3x3."""

@@ -3,7 +3,7 @@
     python tools/bench_dwfwd.py [bf16|f32]
 bf16: the 21 depthwise layers of the MobileNetV3-YOLO 512x512 bs-64 plan (BASELINE configs[3]); f32: those of the MobileNetV2-YOLO
 352x352 bs-256 plan.  Prints ms, algorithmic GB/s and an fp64 checksum of the output and of the statistics rows per shape (A/B runs of
-two builds / two MNY_DW_PF settings must print identical checksums).  Knobs are read once per process: run once per setting."""
+two builds must print identical checksums).  Switches are read once per process: run once per setting."""
 import ctypes
 import os
 import sys

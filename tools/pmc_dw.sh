@@ -7,7 +7,6 @@ run() {  # tag, counter
   rocprofv3 --pmc $2 --output-format csv -d $OUT/pmc_$1_$2 -o run -- python3 $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-nms > /dev/null 2> $OUT/pmc_$1_$2.err
 }
 run A FETCH_SIZE; run A WRITE_SIZE
-export MNY_DW_XCD=0; run B FETCH_SIZE; unset MNY_DW_XCD
 export MNY_DW_V1=1; run D FETCH_SIZE; run D WRITE_SIZE; unset MNY_DW_V1
 cd $OUT
 python3 - <<'PY'
