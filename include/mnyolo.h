@@ -548,6 +548,30 @@ int mny_aug_batch(const uint8_t* src, const mny_aug_item* items, int n_items, co
                   int n_out, int max_in_h, int max_in_w, int canvas, int n_mosaic, int out_h, int out_w,
                   const float* mean3, const float* std3, float* out, void* ws, void* stream);
 
+/* Segmentation maps of a config with a `seg:` section (folder2lmdb.py:99-110,135-141,243-261), for the items and
+ * samples of an mny_aug_batch call.  The uint8 id map of an image has the image's size and makes its geometric trip
+ * (expand_od with border 0, the crop window, the flip; the photometric chain does not touch it); for c = 1..n_classes
+ * the 0/255 image (id == c) is resized to [out_h,out_w] with the arithmetic of OpenCV's INTER_AREA for uchar, one
+ * channel, both scales >= 1 (resize.cpp: per axis the fp64 tap table of computeResizeAreaTab with float weights,
+ * horizontal fp32 sums in tap order, then sum = beta*buf / sum += beta*buf in row order, no FMA, rounded to nearest
+ * even; integer scales on both axes take ResizeAreaFast's round((float)isum * (1.f/area))), and out[...,c-1] =
+ * (float)u8 / 255.0f.  Id 0 and ids above n_classes land in no map.  OpenCV is restated, not linked: the resize half
+ * is parity-unpinned (tests/augment_seg_ref.py holds the same definition in numpy).
+ * seg_src: DEVICE uint8, 4-byte aligned; seg_offsets: DEVICE, per item the byte offset (a multiple of 4) of its
+ * [h,w] id map; the bytes up to the next multiple of 4 after a map must be readable.  Of each item only src.h,
+ * src.w, exp_*, crop_*, flip and sample are read.  n_classes: 1..MNY_AUG_SEG_MAX_CLASSES; out_w * n_classes <= 4096.
+ * Every sample must hold exactly one item (the reference defines no Mosaic with seg maps) and its cropped geometry
+ * must be at least out_h x out_w (a scale below 1 is another OpenCV path, not implemented): such a record is not
+ * read, its maps are written as zeros and the int32 at ws+0 receives 1 + the item index (bad geometry, offset or
+ * bounds) or -(1 + sample index) (bad record), as mny_aug_batch does.  out: [n_out,out_h,out_w,n_classes] fp32,
+ * ready for mny_seg_loss.  ws: mny_aug_seg_ws_bytes() (0 = bad arguments).  No host sync, no allocation;
+ * deterministic launch to launch. */
+#define MNY_AUG_SEG_MAX_CLASSES 8
+size_t mny_aug_seg_ws_bytes(int n_items, int n_out, int n_classes, int max_in_h, int max_in_w, int out_h, int out_w);
+int mny_aug_seg_batch(const uint8_t* seg_src, const int64_t* seg_offsets, const mny_aug_item* items, int n_items,
+                      const mny_aug_sample* samples, int n_out, int n_classes, int max_in_h, int max_in_w, int out_h,
+                      int out_w, float* out, void* ws, void* stream);
+
 /* ---- bf16 STORAGE twins (BASELINE config 4: MobileNetV3-YOLO 512x512 bf16) -----------------
  * Every `mny_X_bf16` has the contract of `mny_X` above with ONE difference: the activation-sized tensors (the
  * `void*` parameters: raw conv outputs, materialised sums, gradients wrt activations) are bf16 in HBM.  Kernels

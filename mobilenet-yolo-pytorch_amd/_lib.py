@@ -124,6 +124,8 @@ _SIGS = {
     "mny_aug_ws_bytes": (c_size_t, [c_int] * 8),
     "mny_aug_photometric": (c_int, [P, P, c_int, c_int, c_int, P, P, P]),
     "mny_aug_batch": (c_int, [P, P, c_int, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, P, P]),
+    "mny_aug_seg_ws_bytes": (c_size_t, [c_int] * 7),
+    "mny_aug_seg_batch": (c_int, [P, P, P, c_int, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P]),
     "mny_eval_pack": (c_int, [P, c_int64, P, c_int64, P, P, P, P, P, P, P]),
 }
 # bf16-storage twins (activation tensors bf16, everything else as in the fp32 entry point): identical ctypes signature

@@ -8,9 +8,16 @@ choice last), and does the box maths with the same torch CPU fp32 ops, so target
 decoded uint8 images into one pinned upload and runs `mny_aug_batch` (csrc/augment.hip): photometric chain, geometry,
 mosaic canvas and the final BILINEAR resize + Normalize, bit for bit against Pillow.
 
+Configs with a `seg:` section (`seg_classes`): every group member also carries its uint8 id map.  The map makes the
+image's geometric trip (expand border 0, crop, flip; no draw of its own, so the plan, the targets and the RNG state are
+those of a plain instance) and `mny_aug_seg_batch` builds collate_fn's per-class maps on the S/16 grid
+(folder2lmdb.py:135-141,243-261).  The geometry is pinned to the reference; the cv2 INTER_AREA resize is restated from
+OpenCV's source (cv2 is not available to pin it), see include/mnyolo.h.  The reference defines no Mosaic with seg maps.
+
 Not covered (stays with the caller): imgaug's `seq` (folder2lmdb.py:28-42, applied to the decoded image before this
-stage, which is the reference's order too), JPEG decoding, the sampler, and seg maps (a config with a `seg:` section
-is refused).  No CPU fallback: without libmnyolo.so every call raises MnyError."""
+stage, which is the reference's order too), JPEG decoding, the sampler, and the scale < 1 path of the area resize (a
+cropped geometry smaller than the S/16 grid is refused).  No CPU fallback: without libmnyolo.so every call raises
+MnyError."""
 import ctypes
 import math
 import random
@@ -29,6 +36,7 @@ ITEM = np.dtype([("offset", np.int64), ("h", np.int32), ("w", np.int32), ("n_ops
                  ("tile", np.int32, 4), ("mask", np.int32, 4)], align=True)                     # mny_aug_item
 SAMPLE = np.dtype([("first_item", np.int32), ("n_items", np.int32), ("canvas_slot", np.int32), ("reserved", np.int32)])
 assert ITEM.itemsize == 392 and SAMPLE.itemsize == 16
+SEG_MAX_CLASSES = 8                                           # MNY_AUG_SEG_MAX_CLASSES
 
 
 def hue_shift_u8(f):
@@ -55,9 +63,13 @@ def _jaccard(set_1, set_2):
 class TrainAugment:
     """aug = TrainAugment.from_config(config)
        images, targets, count = aug(groups)     # groups: [[(uint8 HWC RGB array, target [n,5] cls,cx,cy,w,h)] * 1..4]
-    -> images [N,3,H,W] fp32 on `device`, targets a list of CPU [n,5] float32, count = number of decoded images."""
+    -> images [N,3,H,W] fp32 on `device`, targets a list of CPU [n,5] float32, count = number of decoded images.
+    With `seg_classes` (a config with a `seg:` section) a member is (image, target, seg_id), seg_id the uint8 [h,w] id
+    map of the image, groups hold one image, and the call returns collate_fn's train-phase tuple
+       images, targets, count, seg_maps = aug(groups)     # seg_maps [N,H/16,W/16,seg_classes] fp32 on `device`
+    ready for model(images, targets, seg_maps)."""
 
-    def __init__(self, train_img_size, mean, std, expand_scale, canvas=1000, device="cuda:0", rng=random):
+    def __init__(self, train_img_size, mean, std, expand_scale, canvas=1000, device="cuda:0", rng=random, seg_classes=None):
         self.sizes = [tuple(int(v) for v in s) for s in train_img_size]
         self.mean = (ctypes.c_float * 3)(*[float(v) for v in mean])
         self.std = (ctypes.c_float * 3)(*[float(v) for v in std])
@@ -67,12 +79,26 @@ class TrainAugment:
         self.rng = rng                              # the reference draws from the global `random`
         self._packer = BatchPrep(self.sizes, [0, 0, 0], [1, 1, 1], device=device)
         self._status = None
+        self.seg_classes = None if seg_classes is None else int(seg_classes)
+        if self.seg_classes is not None:
+            if not 1 <= self.seg_classes <= SEG_MAX_CLASSES:
+                raise ValueError("seg_classes must be 1..%d, got %d" % (SEG_MAX_CLASSES, self.seg_classes))
+            if any(h != w for h, w in self.sizes):                         # folder2lmdb.py:244-247 holds for square sizes only
+                raise ValueError("seg maps need square train_img_size entries, got %s" % (self.sizes,))
+        self._seg_stage = None                      # pinned staging buffer of the id maps, grown on demand
+        self._seg_status = None
 
     @classmethod
     def from_config(cls, cfg, **kw):
         if "seg" in cfg:
-            raise ValueError("TrainAugment: configs with a `seg:` section are not supported (the seg-map path, cv2 INTER_AREA "
-                             "resize of the per-class maps, is not implemented on the device)")
+            # train.py:114 hands config["mosaic_num"] to the sampler as the group sizes; Mosaic drops the seg maps and
+            # collate_fn then indexes b[3], so a seg config has to switch Mosaic off itself (models/bdd100k: mosaic_num [1])
+            sizes = cfg.get("mosaic_num")
+            sizes = [sizes] if isinstance(sizes, int) else sizes
+            if not sizes or any(int(v) != 1 for v in sizes):
+                raise ValueError("TrainAugment: a config with a `seg:` section must set mosaic_num: [1] (the reference defines no Mosaic "
+                                 "with seg maps), got mosaic_num=%r" % (cfg.get("mosaic_num"),))
+            kw.setdefault("seg_classes", cfg["seg"]["num_classes"])
         return cls(cfg["train_img_size"], cfg["normalize"]["mean"], cfg["normalize"]["std"], cfg["expand_scale"], **kw)
 
     # ---- host planning (no GPU) -------------------------------------------------------------------------------------
@@ -190,10 +216,22 @@ class TrainAugment:
         return out
 
     def plan(self, groups, size=None):
-        """Host only.  groups: [[(image or (h, w), target)]].  -> dict(items ITEM array (offsets unset), samples SAMPLE
+        """Host only.  groups: [[(image or (h, w), target)]] (with seg_classes a member may carry a third entry, its
+        seg_id, which is checked against the image's size).  -> dict(items ITEM array (offsets unset), samples SAMPLE
         array, targets, count, size, n_mosaic, max_h, max_w)."""
         if len(groups) == 0:
             raise ValueError("empty batch")
+        if self.seg_classes is not None:
+            for g in groups:
+                if len(g) != 1:
+                    raise ValueError("a seg config takes groups of one image (the reference defines no Mosaic with seg maps), got %d" % len(g))
+                for m in g:
+                    if len(m) > 2:
+                        im, sg = m[0], np.asarray(m[2])
+                        hw = (int(im[0]), int(im[1])) if isinstance(im, tuple) else (int(im.shape[0]), int(im.shape[1]))
+                        if sg.dtype != np.uint8 or sg.shape != hw:
+                            raise ValueError("seg_id must be uint8 [h,w] of the image's size %s, got %s %s" % (hw, sg.dtype, sg.shape))
+            groups = [[m[:2] for m in g] for g in groups]
         members, samples, targets, n_mosaic = [], [], [], 0
         for gi, g in enumerate(groups):
             if not 1 <= len(g) <= 4:
@@ -234,6 +272,12 @@ class TrainAugment:
             if "tile" in m:
                 it["tile"] = m["tile"]
                 it["mask"] = m["mask"]
+        if self.seg_classes is not None:
+            gh, gw = int(size[0] / 16), int(size[1] / 16)                # folder2lmdb.py:228
+            for k, m in enumerate(members):
+                if m["geo"][0] < gh or m["geo"][1] < gw:
+                    raise ValueError("image %d: the cropped geometry %dx%d is smaller than the %dx%d seg grid (the scale < 1 path of the "
+                                     "area resize is not implemented)" % (k, m["geo"][0], m["geo"][1], gh, gw))
         max_h = int(max(items["exp"][:, 0].max(), items["h"].max()))
         max_w = int(max(items["exp"][:, 1].max(), items["w"].max()))
         return dict(items=items, samples=np.array(samples, SAMPLE), targets=targets, count=sum(len(g) for g in groups),
@@ -258,17 +302,69 @@ class TrainAugment:
         self._keep = (src, it_dev, sm_dev, ws)
         return out
 
+    def run_device_seg(self, seg_src, seg_offsets, plan, out=None, items_dev=None, samples_dev=None):
+        """seg_src: the packed uint8 id maps on the device; seg_offsets: their byte offsets (int64 array, multiples of 4).
+        -> seg_maps [n_out, out_h/16, out_w/16, seg_classes] fp32 on the device."""
+        if self.seg_classes is None:
+            raise ValueError("this TrainAugment was built without seg_classes")
+        items, samples = plan["items"], plan["samples"]
+        gh, gw = int(plan["size"][0] / 16), int(plan["size"][1] / 16)
+        n_out, C = len(samples), self.seg_classes
+        if out is None:
+            out = torch.empty(n_out, gh, gw, C, device=self.device, dtype=torch.float32)
+        ws = torch.empty(query("mny_aug_seg_ws_bytes", len(items), n_out, C, plan["max_h"], plan["max_w"], gh, gw), device=self.device, dtype=torch.uint8)
+        if items_dev is None:
+            items_dev = torch.from_numpy(items.view(np.uint8).copy()).to(self.device, non_blocking=True)
+        if samples_dev is None:
+            samples_dev = torch.from_numpy(samples.view(np.uint8).copy()).to(self.device, non_blocking=True)
+        off_dev = torch.from_numpy(np.ascontiguousarray(seg_offsets, np.int64)).to(self.device, non_blocking=True)
+        p = lambda t: ctypes.c_void_p(t.data_ptr())
+        call("mny_aug_seg_batch", p(seg_src), p(off_dev), p(items_dev), len(items), p(samples_dev), n_out, C, plan["max_h"], plan["max_w"], gh, gw,
+             p(out), p(ws), ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
+        self._seg_status = ws[:4].view(torch.int32)
+        self._seg_keep = (seg_src, off_dev, items_dev, samples_dev, ws)
+        return out
+
     def pack(self, groups):
         """-> (pinned uint8 staging view, byte offsets of every image in group order)."""
-        stage, desc, _, _ = self._packer.pack([im for g in groups for im, _ in g])
+        stage, desc, _, _ = self._packer.pack([m[0] for g in groups for m in g])
         return stage, desc["offset"]
+
+    def pack_seg(self, groups):
+        """-> (pinned uint8 staging view of the id maps, their byte offsets in group order)."""
+        arrs = []
+        for g in groups:
+            for m in g:
+                if len(m) < 3:
+                    raise ValueError("a seg config takes (image, target, seg_id) members")
+                a = m[2].numpy() if isinstance(m[2], torch.Tensor) else np.asarray(m[2])
+                if a.dtype != np.uint8 or a.shape != tuple(m[0].shape[:2]):
+                    raise ValueError("seg_id must be uint8 [h,w] of the image's size %s, got %s %s" % (tuple(m[0].shape[:2]), a.dtype, a.shape))
+                arrs.append(a)
+        offsets, off = np.zeros(len(arrs), np.int64), 0
+        for i, a in enumerate(arrs):
+            offsets[i] = off
+            off += (a.size + 15) // 16 * 16
+        if self._seg_stage is None or self._seg_stage.numel() < off:
+            self._seg_stage = torch.empty(max(off, 1 << 20), dtype=torch.uint8)
+            if torch.cuda.is_available():
+                self._seg_stage = self._seg_stage.pin_memory()
+        buf = self._seg_stage.numpy()
+        for o, a in zip(offsets, arrs):
+            buf[o:o + a.size] = a.reshape(-1)
+        return self._seg_stage[:off], offsets
 
     def __call__(self, groups, size=None):
         plan = self.plan(groups, size)
         stage, offsets = self.pack(groups)
         plan["items"]["offset"] = offsets
+        if self.seg_classes is None:
+            images = self.run_device(stage.to(self.device, non_blocking=True), plan)
+            return images, plan["targets"], plan["count"]
+        seg_stage, seg_offsets = self.pack_seg(groups)
         images = self.run_device(stage.to(self.device, non_blocking=True), plan)
-        return images, plan["targets"], plan["count"]
+        seg_maps = self.run_device_seg(seg_stage.to(self.device, non_blocking=True), seg_offsets, plan, items_dev=self._keep[1], samples_dev=self._keep[2])
+        return images, plan["targets"], plan["count"], seg_maps
 
     def check(self):
         """Host sync: raise if the last batch held an image or record outside the declared bounds."""
@@ -278,3 +374,9 @@ class TrainAugment:
                 raise RuntimeError("augment: image %d is empty, misaligned or larger than the declared maximum" % (v - 1))
             if v < 0:
                 raise RuntimeError("augment: sample record %d is malformed" % (-v - 1))
+        if self._seg_status is not None:
+            v = int(self._seg_status.item())
+            if v > 0:
+                raise RuntimeError("augment: seg map %d is misaligned, outside the declared maximum or smaller than the seg grid" % (v - 1))
+            if v < 0:
+                raise RuntimeError("augment: sample record %d is malformed for the seg maps (one image per sample)" % (-v - 1))

@@ -1,4 +1,4 @@
-// Device-side training augmentation (include/mnyolo.h: mny_aug_photometric / mny_aug_batch).
+// Device-side training augmentation (include/mnyolo.h: mny_aug_photometric / mny_aug_batch / mny_aug_seg_batch).
 // Replaces the pixel half of the reference's train-phase sample path (image_augmentation.py transform_od + Mosaic,
 // folder2lmdb.py collate_fn); the host made every random draw.  Launch sequence of mny_aug_batch:
 //   lsum    : per item with a contrast op, the integer sum of L over the image after the ops before it
@@ -9,6 +9,8 @@
 // The resample passes read the source THROUGH the geometry (expand canvas + filler 127, crop window, flip) and compute
 // their Pillow taps (Resample.c precompute_coeffs + normalize_coeffs_8bpc, fp64) per output index in the thread that
 // uses them.  An axis whose size does not change gets the taps {1 << 22, 0, ...}: bit-identical to Pillow skipping it.
+// mny_aug_seg_batch (one launch, aug_seg_kernel) gives the same items' id maps the geometric trip and OpenCV's INTER_AREA
+// resize per class; see the section below.
 // Integer work throughout; the fp32/fp64 arithmetic mirrors Pillow's C statement by statement, so the file is compiled
 // with -ffp-contract=off.
 #include "common.h"
@@ -460,6 +462,152 @@ __global__ __launch_bounds__(256) void aug_fill_kernel(const mny_aug_item* __res
     o[0] = o[1] = o[2] = 0;                                                                                 // np.zeros background
 }
 
+// ---- segmentation maps (mny_aug_seg_batch) -----------------------------------------------------------------------
+// The id map makes the image's geometric trip (expand border 0, crop window, flip); per class c = 1..C the 0/255 image
+// (id == c) is resized with OpenCV's INTER_AREA (resize.cpp computeResizeAreaTab / ResizeArea_, ResizeAreaFast_) and
+// divided by 255.  One block per (sample, destination row): the threads split the band's (source row, dx) pairs, each
+// reads its ids ONCE for all classes and forms the horizontal sums in tap order into LDS; then one thread per (dx, c)
+// runs the vertical accumulation in row order.  Bands taller than the LDS buffer are walked in chunks, `sum` carried.
+constexpr int kSegLds = 8192;                // floats: per (dx, c) the carried sum, then R rows of horizontal sums
+constexpr int kSegMaxClasses = MNY_AUG_SEG_MAX_CLASSES;
+
+__device__ __forceinline__ double area_scale(int ssize, int dsize) { return 1.0 / ((double)dsize / (double)ssize); }
+
+__device__ __forceinline__ bool area_fast(int ssize, int dsize) {
+    const double scale = area_scale(ssize, dsize);
+    return fabs(scale - (double)(int)scale) < 2.220446049250313e-16;                           // DBL_EPSILON
+}
+
+// The taps of one destination index in emission order: source indices start .. start + n - 1, the first / last one
+// partial (lo / hi).  `fast`: the integer-scale cell, weights unused.
+struct area_taps {
+    int start, n, lo, hi;
+    float a_lo, a_mid, a_hi;
+    __device__ __forceinline__ area_taps(int ssize, int dsize, int d, bool fast) {
+        const double scale = area_scale(ssize, dsize);
+        lo = hi = 0;
+        a_lo = a_mid = a_hi = 0.f;
+        if (fast) {
+            n = (int)scale;
+            start = d * n;
+            return;
+        }
+        const double f1 = d * scale, f2 = f1 + scale;
+        const double cell = fmin(scale, ssize - f1);
+        int s1 = (int)ceil(f1);
+        const int s2 = min((int)floor(f2), ssize - 1);
+        s1 = min(s1, s2);
+        lo = s1 - f1 > 1e-3;
+        hi = f2 - s2 > 1e-3;
+        a_lo = (float)((s1 - f1) / cell);
+        a_mid = (float)(1.0 / cell);
+        a_hi = (float)(fmin(fmin(f2 - s2, 1.0), cell) / cell);
+        start = s1 - lo;
+        n = lo + (s2 - s1) + hi;
+    }
+    __device__ __forceinline__ float k(int t) const { return (lo && t == 0) ? a_lo : ((hi && t == n - 1) ? a_hi : a_mid); }
+};
+
+__device__ bool seg_geo_ok(const mny_aug_item& it, int64_t off, int max_h, int max_w, int out_h, int out_w) {
+    if (it.src.h < 1 || it.src.w < 1 || it.src.h > max_h || it.src.w > max_w || (off & 3) || off < 0) return false;
+    if (it.exp_h < it.src.h || it.exp_w < it.src.w || it.exp_h > max_h || it.exp_w > max_w) return false;
+    if (it.exp_top < 0 || it.exp_left < 0 || it.exp_top + it.src.h > it.exp_h || it.exp_left + it.src.w > it.exp_w) return false;
+    if (it.crop_top < 0 || it.crop_left < 0 || it.crop_h < out_h || it.crop_w < out_w) return false;      // scale < 1: another OpenCV path
+    return it.crop_top + it.crop_h <= it.exp_h && it.crop_left + it.crop_w <= it.exp_w;
+}
+
+// grid (out_h, n_out), 256 threads
+__global__ __launch_bounds__(256) void aug_seg_kernel(const uint8_t* __restrict__ seg, const int64_t* __restrict__ offs,
+                                                      const mny_aug_item* __restrict__ items, int n_items, const mny_aug_sample* __restrict__ samples,
+                                                      int C, int max_h, int max_w, int out_h, int out_w, float* __restrict__ out, char* __restrict__ ws) {
+    __shared__ float lds[kSegLds];
+    const int si = blockIdx.y, dy = blockIdx.x, tid = threadIdx.x;
+    const int WC = out_w * C;
+    float* o = out + ((size_t)si * out_h + dy) * WC;
+    const mny_aug_sample s = samples[si];
+    int bad = 0;
+    if (s.n_items != 1 || s.first_item < 0 || s.first_item >= n_items) bad = -(1 + si);
+    else if (items[s.first_item].sample != si) bad = -(1 + si);
+    else if (!seg_geo_ok(items[s.first_item], offs[s.first_item], max_h, max_w, out_h, out_w)) bad = 1 + s.first_item;
+    if (bad) {                                                                      // block-uniform: the row is zeros, nothing is read
+        if (dy == 0 && tid == 0) flag(ws, bad);
+        for (int e = tid; e < WC; e += 256) o[e] = 0.f;
+        return;
+    }
+    const mny_aug_item& it = items[s.first_item];
+    const int64_t off = offs[s.first_item];
+    const int h = it.src.h, w = it.src.w, ch = it.crop_h, cw = it.crop_w;
+    const int ox = it.crop_left - it.exp_left, oy = it.crop_top - it.exp_top, flip = it.flip;
+    const bool fast = area_fast(ch, out_h) && area_fast(cw, out_w);
+    const area_taps ty(ch, out_h, dy, fast);
+    const uint32_t* words = (const uint32_t*)seg;                                   // seg and every offset are 4-byte aligned
+    float* sum = lds;
+    float* buf = lds + WC;
+    const int R = (kSegLds - WC) / WC;                                              // >= 1 (checked on the host)
+    for (int e = tid; e < WC; e += 256) sum[e] = 0.f;                               // the bits of int 0 too; owner-only from here on
+    for (int r0 = 0; r0 < ty.n; r0 += R) {
+        const int nr = min(R, ty.n - r0);
+        __syncthreads();                                                            // the previous chunk has been consumed
+        for (int p = tid; p < nr * out_w; p += 256) {
+            const int r = p / out_w, dx = p - r * out_w;
+            const area_taps tx(cw, out_w, dx, fast);
+            const int y = ty.start + r0 + r, yy = y + oy;
+            float acc[kSegMaxClasses];
+            int cnt[kSegMaxClasses];
+#pragma unroll
+            for (int c = 0; c < kSegMaxClasses; ++c) { acc[c] = 0.f; cnt[c] = 0; }
+            if (y >= 0 && y < ch && yy >= 0 && yy < h) {
+                const int64_t row = off + (int64_t)yy * w;
+                int64_t have = -1;
+                uint32_t word = 0;
+                for (int t = 0; t < tx.n; ++t) {
+                    const int x = tx.start + t;
+                    const int xx = (flip ? cw - 1 - x : x) + ox;
+                    if (x < 0 || x >= cw || xx < 0 || xx >= w) continue;            // border: 0 in every class
+                    const int64_t a = row + xx;
+                    if ((a >> 2) != have) { have = a >> 2; word = words[have]; }
+                    const int id = (word >> (8 * (int)(a & 3))) & 255;
+                    if (fast) {
+#pragma unroll
+                        for (int c = 0; c < kSegMaxClasses; ++c) cnt[c] += id == c + 1;
+                    } else {
+                        const float v = 255.f * tx.k(t);
+#pragma unroll
+                        for (int c = 0; c < kSegMaxClasses; ++c) acc[c] = acc[c] + (id == c + 1 ? v : 0.f);
+                    }
+                }
+            }
+            float* b = buf + (size_t)p * C;
+#pragma unroll
+            for (int c = 0; c < kSegMaxClasses; ++c)
+                if (c < C) b[c] = fast ? __int_as_float(cnt[c]) : acc[c];
+        }
+        __syncthreads();
+        for (int e = tid; e < WC; e += 256) {
+            if (fast) {
+                int isum = __float_as_int(sum[e]);
+                for (int r = 0; r < nr; ++r) isum += __float_as_int(buf[r * WC + e]);
+                sum[e] = __int_as_float(isum);
+            } else {
+                float v = sum[e];
+                for (int r = 0; r < nr; ++r) {
+                    const float beta = ty.k(r0 + r), bv = buf[r * WC + e];
+                    v = r0 + r == 0 ? beta * bv : v + beta * bv;
+                }
+                sum[e] = v;
+            }
+        }
+    }
+    const area_taps tx0(cw, out_w, 0, fast);
+    for (int e = tid; e < WC; e += 256) {
+        float v = sum[e];
+        if (fast) v = (float)(255 * __float_as_int(v)) * (1.f / (float)(tx0.n * ty.n));
+        v = rintf(v);                                                               // saturate_cast<uchar>: nearest even, clamped
+        v = v < 0.f ? 0.f : (v > 255.f ? 255.f : v);
+        o[e] = v / 255.0f;
+    }
+}
+
 }  // namespace
 }  // namespace mny
 
@@ -517,4 +665,26 @@ extern "C" int mny_aug_batch(const uint8_t* src, const mny_aug_item* items, int 
         items, n_items, samples, n_mosaic, max_in_h, max_in_w, canvas, out_h, out_w, L, w, make_float3(mean3[0], mean3[1], mean3[2]),
         make_float3(std3[0], std3[1], std3[2]), out);
     return check_launch("mny_aug_batch");
+}
+
+extern "C" size_t mny_aug_seg_ws_bytes(int n_items, int n_out, int n_classes, int max_in_h, int max_in_w, int out_h, int out_w) {
+    if (n_items < 1 || n_out < 1 || n_classes < 1 || n_classes > kSegMaxClasses || max_in_h < 1 || max_in_w < 1 || out_h < 1 || out_w < 1) return 0;
+    return 256;                                                                     // the status word
+}
+
+extern "C" int mny_aug_seg_batch(const uint8_t* seg_src, const int64_t* seg_offsets, const mny_aug_item* items, int n_items, const mny_aug_sample* samples,
+                                 int n_out, int n_classes, int max_in_h, int max_in_w, int out_h, int out_w, float* out, void* ws, void* stream) {
+    MNY_REQUIRE(seg_src && seg_offsets && items && samples && out && ws, "mny_aug_seg_batch: null pointer");
+    MNY_REQUIRE(((uintptr_t)seg_src & 3) == 0, "mny_aug_seg_batch: seg_src must be 4-byte aligned");
+    MNY_REQUIRE(n_classes >= 1 && n_classes <= kSegMaxClasses, "mny_aug_seg_batch: n_classes=%d outside 1..%d", n_classes, kSegMaxClasses);
+    MNY_REQUIRE(n_items >= 1 && n_items <= 65535 && n_out >= 1 && n_out <= 65535 && max_in_h >= 1 && max_in_w >= 1 && out_h >= 1 && out_w >= 1 &&
+                    (int64_t)max_in_h * max_in_w < ((int64_t)1 << 31),
+                "mny_aug_seg_batch: bad sizes items=%d out=%d in<=%dx%d out=%dx%d", n_items, n_out, max_in_h, max_in_w, out_h, out_w);
+    MNY_REQUIRE((int64_t)out_w * n_classes * 2 <= kSegLds, "mny_aug_seg_batch: out_w * n_classes = %lld exceeds %d", (long long)out_w * n_classes,
+                kSegLds / 2);
+    hipStream_t st = (hipStream_t)stream;
+    if (hipMemsetAsync(ws, 0, 256, st) != hipSuccess) { set_error("mny_aug_seg_batch: memset failed"); return MNY_EHIP; }
+    aug_seg_kernel<<<dim3(out_h, n_out), 256, 0, st>>>(seg_src, seg_offsets, items, n_items, samples, n_classes, max_in_h, max_in_w, out_h, out_w, out,
+                                                       (char*)ws);
+    return check_launch("mny_aug_seg_batch");
 }
