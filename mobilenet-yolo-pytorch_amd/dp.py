@@ -97,7 +97,7 @@ class PlanReducer:
     def slot_extents(plan):
         """Floats each gradient slot occupies in the arena, in arena order, taken from the REAL layout: next slot's offset
         minus this slot's, the arena's end closing the last one.  (The engine pads slots to 16 bytes and reserves slack behind
-        the padded detection-head gradients — engine._build_backward — so sizes recomputed from numel() fall short.)"""
+        the padded detection-head gradients — engine.NetPlan._plan_grad_arena — so sizes recomputed from numel() fall short.)"""
         offs = [plan.grad_slots[n][0] for n in plan.grad_params]
         assert offs == sorted(offs) and (not offs or offs[0] == 0), "arena slots must be laid out in grad_params order"
         ends = offs[1:] + [plan.gflat.numel()]

@@ -55,7 +55,7 @@ class FakePlan:
         slack = slack or {}
         for i, (n, s) in enumerate(zip(self.grad_params, sizes)):
             self.grad_slots[n] = (off, s)
-            off += (max(s, slack.get(i, 0)) + 3) // 4 * 4       # engine._build_backward: padded detection heads reserve slack
+            off += (max(s, slack.get(i, 0)) + 3) // 4 * 4       # engine.NetPlan._plan_grad_arena: padded detection heads reserve slack
         self.gflat = torch.zeros(off)
         self.gviews = {n: self.gflat[o:o + s] for n, (o, s) in self.grad_slots.items()}
         # two calls per slot: a no-op and the producing call (so ready indices are not trivially i+1)
