@@ -369,6 +369,29 @@ typedef struct mny_adamw_chunk {
 int mny_adamw_step(const mny_adamw_chunk* table_dev, int nchunks, double lr, double beta1, double beta2, double eps,
                    double weight_decay, int64_t step, void* stream);
 
+/* ---- fused gradient clipping (torch.nn.utils.clip_grad_norm_, L2, in two launches) ----------------------------
+ * `segs_dev` is a DEVICE array of gradient segments: g[0..n) fp32, 4-byte aligned, any n >= 0.  A segment of n floats
+ * is cut into mny_grad_clip_parts(n) blocks of MNY_CLIP_BLOCK floats; `block0` is the number of blocks of the
+ * segments in front of it (non-decreasing, 0 for the first) and `nblocks` their total.  Nothing outside
+ * [g, g + n) is read or written, so slack between segments never enters the norm.
+ * Launch 1: one workgroup per block leaves the block's sum of squares in ws[block] (double): a fixed partition
+ * summed in a fixed order — a thread's fp32 accumulator takes at most MNY_CLIP_TERMS squares, everything across
+ * threads and blocks is fp64 — so two runs agree bit for bit.  Launch 2: every workgroup combines ws[] the same
+ * way, out[0] = total_norm = (float)sqrt(sum), out[1] = coef = min(1, max_norm / (total_norm + 1e-6)) with one
+ * correctly rounded fp32 division (torch multiplies max_norm by the rounded reciprocal, which can differ in the last bit; out[1] is the
+ * factor that was applied).  A non-finite norm propagates as it does in torch: NaN stays NaN.  g *= coef in place unless coef == 1.
+ * `ws`: nblocks doubles; `out`: 2 floats; both device memory.  No host synchronisation.                        */
+#define MNY_CLIP_BLOCK 8192
+#define MNY_CLIP_TERMS 34 /* 8 float4 of the 16-byte aligned body + one scalar each of its head and tail */
+typedef struct mny_clip_seg {
+    float* g;
+    int64_t n;
+    int32_t block0;
+    int32_t pad;
+} mny_clip_seg;
+int mny_grad_clip_parts(int64_t n);
+int mny_grad_clip(const mny_clip_seg* segs_dev, int nsegs, int nblocks, double max_norm, double* ws, float* out, void* stream);
+
 /* ---- data-gradient GEMM + BN-backward reduction of the unit it feeds ------------------------------------------
  * dx[M,Nc] = dy[M,K] * W, with W^T given as [Nc][K] rows (mny_transpose of the conv weight) — the autograd
  * data gradient of nn.Conv2d(Nc,K,1) (mobilenetv2.py:69,83) — when dx is the complete gradient of a

@@ -43,6 +43,89 @@ __global__ __launch_bounds__(256) void adamw_kernel(const mny_adamw_chunk* __res
     }
 }
 
+// ---- fused gradient clipping (mny_grad_clip): two streaming passes over the gradient segments, HBM-bound ----
+// One workgroup per MNY_CLIP_BLOCK floats of a segment.  The block's first element sits (block index) * 8192 floats behind the
+// segment's, so every block of a segment has the segment's alignment: up to 3 scalar head elements reach the 16-byte boundary,
+// float4 loads / stores cover the body, up to 3 scalars the tail.
+struct clip_span {
+    float* g;          // first element of this workgroup's block
+    int cnt, head, n4; // elements, scalar head elements, float4 of the body
+};
+
+__device__ __forceinline__ clip_span clip_find(const mny_clip_seg* __restrict__ segs, int nsegs, int b) {
+    int lo = 0, hi = nsegs - 1;                                  // the last segment whose block0 <= b
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (segs[mid].block0 <= b) lo = mid; else hi = mid - 1;
+    }
+    const mny_clip_seg sg = segs[lo];
+    const int64_t off = (int64_t)(b - sg.block0) * MNY_CLIP_BLOCK;
+    int64_t left = sg.n - off;                                   // (a table whose block0 column disagrees with the lengths yields empty blocks, never an access outside a segment)
+    if (b < sg.block0 || left < 0) left = 0;
+    clip_span sp;
+    sp.cnt = (int)(left < MNY_CLIP_BLOCK ? left : MNY_CLIP_BLOCK);
+    sp.g = sg.g + off;
+    const int mis = (int)((reinterpret_cast<uintptr_t>(sp.g) >> 2) & 3);
+    const int head = (4 - mis) & 3;
+    sp.head = head < sp.cnt ? head : sp.cnt;
+    sp.n4 = (sp.cnt - sp.head) >> 2;
+    return sp;
+}
+
+// fixed-order fp64 tree over the workgroup's 256 values; every thread returns the total
+__device__ __forceinline__ double clip_block_sum(double v, double* sh) {
+    const int t = threadIdx.x;
+    sh[t] = v;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (t < s) sh[t] += sh[t + s];
+        __syncthreads();
+    }
+    const double r = sh[0];
+    __syncthreads();
+    return r;
+}
+
+__global__ __launch_bounds__(256) void clip_sumsq_kernel(const mny_clip_seg* __restrict__ segs, int nsegs, double* __restrict__ ws) {
+    __shared__ double sh[256];
+    const clip_span sp = clip_find(segs, nsegs, blockIdx.x);
+    const int t = threadIdx.x;
+    const float* __restrict__ body = sp.g + sp.head;
+    float acc = 0.f;                                             // <= 8 float4 + 1 head + 1 tail scalar = MNY_CLIP_TERMS squares
+    for (int i = t; i < sp.n4; i += 256) {
+        const float4 v = ld4(body + 4 * i);
+        acc = fmaf(v.x, v.x, acc); acc = fmaf(v.y, v.y, acc); acc = fmaf(v.z, v.z, acc); acc = fmaf(v.w, v.w, acc);
+    }
+    if (t < sp.head) acc = fmaf(sp.g[t], sp.g[t], acc);
+    const int ts = sp.head + 4 * sp.n4;
+    if (t < sp.cnt - ts) acc = fmaf(sp.g[ts + t], sp.g[ts + t], acc);
+    const double tot = clip_block_sum((double)acc, sh);
+    if (t == 0) ws[blockIdx.x] = tot;
+}
+
+__global__ __launch_bounds__(256) void clip_scale_kernel(const mny_clip_seg* __restrict__ segs, int nsegs, const double* __restrict__ ws, int nblocks,
+                                                        float max_norm, float* __restrict__ out) {
+    __shared__ double sh[256];
+    const int t = threadIdx.x;
+    double s = 0.0;
+    for (int i = t; i < nblocks; i += 256) s += ws[i];           // the same order in every workgroup: they all form the same coefficient
+    const float tn = (float)sqrt(clip_block_sum(s, sh));
+    float coef = max_norm / (tn + 1e-6f);
+    coef = coef > 1.f ? 1.f : coef;                              // torch.clamp(max=1): NaN stays NaN
+    if (blockIdx.x == 0 && t == 0) { out[0] = tn; out[1] = coef; }
+    if (coef == 1.f) return;                                     // nothing to scale (g * 1 is g)
+    const clip_span sp = clip_find(segs, nsegs, blockIdx.x);
+    float* body = sp.g + sp.head;
+    for (int i = t; i < sp.n4; i += 256) {
+        float4 v = ld4(body + 4 * i);
+        v.x *= coef; v.y *= coef; v.z *= coef; v.w *= coef;
+        st4(body + 4 * i, v);
+    }
+    if (t < sp.head) sp.g[t] *= coef;
+    const int ts = sp.head + 4 * sp.n4;
+    if (t < sp.cnt - ts) sp.g[ts + t] *= coef;
+}
+
 }  // namespace mny
 
 using namespace mny;
@@ -56,4 +139,19 @@ extern "C" int mny_adamw_step(const mny_adamw_chunk* table_dev, int nchunks, dou
     hipLaunchKernelGGL(adamw_kernel, dim3(nchunks), dim3(256), 0, (hipStream_t)stream, table_dev, nchunks, (float)(1.0 - lr * weight_decay),
                        (float)(lr / bc1), (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)(1.0 / sqrt(bc2)), (float)eps);
     return check_launch("adamw_kernel");
+}
+
+extern "C" int mny_grad_clip_parts(int64_t n) {
+    MNY_REQUIRE(n >= 0 && n / MNY_CLIP_BLOCK < (1 << 30), "grad_clip_parts: bad length");
+    return (int)((n + MNY_CLIP_BLOCK - 1) / MNY_CLIP_BLOCK);
+}
+
+extern "C" int mny_grad_clip(const mny_clip_seg* segs_dev, int nsegs, int nblocks, double max_norm, double* ws, float* out, void* stream) {
+    MNY_REQUIRE(segs_dev && ws && out, "grad_clip: null pointer");
+    MNY_REQUIRE(nsegs > 0 && nblocks > 0, "grad_clip: empty segment table");
+    MNY_REQUIRE(max_norm >= 0.0, "grad_clip: max_norm must be >= 0");          // (a NaN max_norm fails this too)
+    hipLaunchKernelGGL(clip_sumsq_kernel, dim3(nblocks), dim3(256), 0, (hipStream_t)stream, segs_dev, nsegs, ws);
+    if (int rc = check_launch("clip_sumsq_kernel")) return rc;
+    hipLaunchKernelGGL(clip_scale_kernel, dim3(nblocks), dim3(256), 0, (hipStream_t)stream, segs_dev, nsegs, ws, nblocks, (float)max_norm, out);
+    return check_launch("clip_scale_kernel");
 }

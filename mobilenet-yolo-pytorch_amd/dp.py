@@ -136,6 +136,16 @@ class PlanReducer:
         self.ar.wait()
 
 
+_attached = weakref.WeakSet()      # every live _ModelReducer of the process (wait_pending)
+
+
+def wait_pending():
+    """Make the current stream wait for the pending gradient all-reduces of every model with data-parallel gradients attached: what
+    code that is handed bare parameters (optim.clip_grad_norm_(model.parameters(), ...)) calls before it reads or scales their .grad."""
+    for red in list(_attached):
+        red.wait()
+
+
 class _ModelReducer:
     """Per-model handle returned by attach_data_parallel.  The PlanReducer of a plan is OWNED BY THE PLAN (`plan._dp`); this object
     only keeps weak references, so a plan evicted from the model's plan cache (multi-scale training: one ~40 GB plan per size at
@@ -178,6 +188,7 @@ def attach_data_parallel(model, group=None, n_buckets=4):
             dist.broadcast(t, src=0, group=group)
     red = _ModelReducer(model, group, n_buckets)
     model.dp_reducer = red
+    _attached.add(red)
     ref = weakref.ref(red)
 
     def _before_optimizer_step(_opt, _args, _kwargs):

@@ -27,7 +27,7 @@ import warnings
 import numpy as np
 import torch
 
-from . import _lib, switches
+from . import _lib, frontier, switches
 from ._lib import ACT_NONE, MnyError, YoloHead
 
 _FWD_TICK = itertools.count()            # process-wide order of training forwards (NetPlan.last_fwd_tick)
@@ -227,15 +227,22 @@ _HARD = (_lib.ACT_HSWISH, _lib.ACT_HSIGMOID)
 
 
 class NetPlan:
-    def __init__(self, net, N, H, W, training, act_dtype=torch.float32, bn_batch=None, frozen_bwd=False):
+    def __init__(self, net, N, H, W, training, act_dtype=torch.float32, bn_batch=None, frozen_bwd=False, frozen_params=(), bn_eval=()):
         """training: build the loss calls (else decode + NMS).  bn_batch (default = training): BatchNorm on batch statistics
         with the running-statistics update, and the backward list; False with training=True is the "validation loss" plan
         (running statistics, buffers untouched) — forward only, or with frozen_bwd the backward list of frozen BatchNorm
-        (the statistics are constants of the step: mbv2_yolo.py:157 under model.eval() with gradients)."""
+        (the statistics are constants of the step: mbv2_yolo.py:157 under model.eval() with gradients).
+        frozen_params: names of the parameters with requires_grad == False — the backward list stops at the frontier they leave
+        (frontier.py) and the gradient arena lists only the others.  bn_eval: names of the BatchNorm modules in eval mode while the plan
+        runs on batch statistics: those units normalise with their running statistics and update nothing (below the frontier only)."""
         self.net, self.N, self.H, self.W, self.training = net, N, H, W, training
         bn_batch = training if bn_batch is None else bool(bn_batch)      # (bn_batch without training: decode + NMS on batch statistics, model.train()(images))
         self.bn_batch = bn_batch
         self.frozen = bool(training and not bn_batch and frozen_bwd)
+        self.frontier = frontier.Frontier(net.graph, frozen_params)
+        self.bn_eval = frozenset(bn_eval) if bn_batch else frozenset()
+        if training and bn_batch:
+            frontier.check_bn_modes(net.graph, self.frontier, self.bn_eval)
         self.fwd_gen = 0
         self.inflight_gen = None                # model._InFlight: forward generation whose backward is still owed
         self.last_fwd_tick = -1                 # process-wide order of training forwards (model._grad_plan picks the oldest when every slot is busy)
@@ -309,6 +316,10 @@ class NetPlan:
         self._analyse_graph(g)
         self._match_exdw(g, sw_exdw_k)
         self._match_gates(g, sw_no_gate)
+        for pid, d in self.exdw_pw.items():          # fused multi-BatchNorm units of the forward pass: their members share one mode
+            frontier.check_fused_pair([g.values[pid].node.bn, d.bn], self.bn_eval, "expand + depthwise")
+        for gate in self.gates.values():
+            frontier.check_fused_pair([gate["se0"].bn, gate["se3"].bn], self.bn_eval, "gate")
         # Nodes no loss (or detection output) depends on — MobileNetV2-YOLO's always-on seg branch under a config without a `seg` section
         # (mbv2_yolo.py:155-156: computed, BatchNorm running statistics updated, result dropped) — feed nothing on the main stream: in a
         # training plan they run on the SIDE stream next to the rest of the forward pass (their own statistics workspace), joined behind the heads.
@@ -324,7 +335,7 @@ class NetPlan:
         self._build_detection()
         if dead_forked or self._loss_side:
             self.fwd.add_py(self._join_side, "join")                    # the dead branch's tensors (and the workspace it used) are free again before anything reuses them
-        if training and (bn_batch or self.frozen):
+        if training and (bn_batch or self.frozen) and self.frontier.order:      # (nothing trainable a loss depends on: forward only)
             self._build_backward(g)
 
     def _shape(self, v):
@@ -461,16 +472,24 @@ class NetPlan:
         self.reals[o.id] = t
         return t
 
+    def _batch_stats(self, bn):
+        """Does the BatchNorm module `bn` normalise with (and update its running statistics from) the batch's statistics in this plan?"""
+        return self.bn_batch and bn not in self.bn_eval
+
     def _emit_bn_tail(self, bn, u, parts, M, sws, st):
         """Behind a unit's forward conv: batch statistics -> coefficients and running statistics, or the coefficients of the running ones."""
         P = self._P
         gam, bet, rm, rv = P[bn + ".weight"], P[bn + ".bias"], P[bn + ".running_mean"], P[bn + ".running_var"]
-        if self.bn_batch:
+        if self._batch_stats(bn):
             self.fwd.add("mny_bn_finalize", sws, parts, M, gam, bet, BN_EPS, BN_MOMENTUM, rm, rv, u.scale, u.shift, u.mean, u.invstd, u.C, st)
         else:
-            self.fwd.add("mny_bn_eval_coeffs", gam, bet, rm, rv, BN_EPS, u.scale, u.shift, u.C, self.stream)
+            self.fwd.add("mny_bn_eval_coeffs", gam, bet, rm, rv, BN_EPS, u.scale, u.shift, u.C, st)       # (st: an eval-mode unit of the dead branch stays on its stream)
             if self.frozen:                          # the backward kernels' yhat = (y - running_mean) * invstd
-                self.fwd.add("mny_bn_eval_stats", rm, rv, BN_EPS, u.mean, u.invstd, u.C, self.stream)
+                self.fwd.add("mny_bn_eval_stats", rm, rv, BN_EPS, u.mean, u.invstd, u.C, st)
+            # An eval-mode unit of a batch-statistics plan sits below the frontier (check_bn_modes) and has no backward call, so its
+            # u.mean / u.invstd stay unwritten on purpose.  The only readers are the fused `_red` data-gradient kernels of the units right
+            # above the frontier (mny_pw_bnbwd_red, mny_dw_bnbwd_red, mny_exdw_bwd_red, mny_pw_lr_fix), which form this unit's BN-backward
+            # sums as a by-product: those sums are never consumed (no finalize runs for this unit), whatever they were computed from.
 
     def _emit_pw_gemm(self, calls, x, wop, w6, bias, addend, out, stats, M, K, Nc, st, tag=""):
         """out[M][Nc] = view(x)[M][K] . wop^T (+ bias) (+ addend): the pointwise forward GEMM, also the plain data gradient (x = dY, wop = W^T).
@@ -488,7 +507,7 @@ class NetPlan:
         """stem / depthwise / pointwise conv + BatchNorm (+ activation, applied by the consumers' views)."""
         o = nd.out
         u = self._new_unit(o, materialise=o.id not in self.exdw_pw)      # the expand output of an exdw unit is never materialised
-        stats = sws if self.bn_batch else None
+        stats = sws if self._batch_stats(nd.bn) else None
         if nd.op == "stem":
             conv = self._fwd_stem
         elif nd.op == "dw":
@@ -530,7 +549,7 @@ class NetPlan:
         i = nd.ins[0]
         xv = self._view(i)
         M, C = u.M, u.C
-        if self.bn_batch:                            # batch statistics of the un-materialised expand output (eval plans use the running ones)
+        if stats is not None:                        # batch statistics of the un-materialised expand output (eval plans / eval-mode units use the running ones)
             self.fwd.add("mny_exdw_stats", xv[0], xv[1], xv[2], xv[3], w, stats, M, i.C, C, self.stream,
                          meta=dict(flops=2 * M * i.C * (i.C + 1), bytes=self.eb * M * i.C,      # X^T X and colsum(X): one read of the thin X
                                    shape="exdw stats M%d K%d N%d" % (M, i.C, C)))
@@ -592,10 +611,10 @@ class NetPlan:
         parts = _lib.query("mny_gate_parts", M)
         eb = self.eb
         for un, hn in ((u1, se0), (u2, se3)):
-            if self.bn_batch and hn is se0:
+            if self._batch_stats(hn.bn) and hn is se0:
                 self.fwd.add("mny_gate_stats1_bf16", tv[0], tv[1], tv[2], wq, self.stats_ws, M, C, R, self.stream,
                              meta=dict(flops=2 * M * C * R, bytes=eb * M * C, shape="gate stats1 M%d C%d R%d" % (M, C, R)))
-            elif self.bn_batch:
+            elif self._batch_stats(hn.bn):
                 self.fwd.add("mny_gate_stats2_bf16", tv[0], tv[1], tv[2], wq, u1.scale, u1.shift, self.stats_ws, M, C, R, self.stream,
                              meta=dict(flops=4 * M * C * R, bytes=eb * M * C, shape="gate stats2 M%d C%d R%d" % (M, C, R)))
             self._emit_bn_tail(hn.bn, un, parts, M, self.stats_ws, self.stream)
@@ -692,15 +711,17 @@ class NetPlan:
         """State of the backward builder (all of it initialised here), the gradients of the loss inputs, then per node: the unit's emitter
         (_bwd_emitter) and the common tail."""
         bwd = self.bwd = CallList()
-        order = self.bwd_order
+        fr = self.frontier
+        order = fr.order             # == self.bwd_order with every parameter trainable; else cut at the frontier (frontier.py)
         self._plan_grad_arena(order)
         self._written = set()        # parameter names whose arena slot has its first contribution
         self.shared_tmp = []         # (scratch, arena view): later contributions of a module applied twice, added in by _flush_shared
         self._red_jobs, self._red_keep, self._post_reduce = [], [], []     # deferred partial combines (_defer_job / _flush_reduce)
         self._uses = {}              # conv name -> applications (a module applied twice, mbv3_yolo.py:133-134, adds a second contribution
-        for nd in order:             # right after its producing call: its combines stay inline)
-            if nd.conv:
-                self._uses[nd.conv] = self._uses.get(nd.conv, 0) + 1
+        for nd in self.bwd_order:    # right after its producing call: its combines stay inline).  Counted over the whole graph, not the part
+            if nd.conv:              # above the frontier: a unit that straddles it is emitted exactly as in the full plan, its unwanted
+                self._uses[nd.conv] = self._uses.get(nd.conv, 0) + 1      # outputs (data gradient, BN sums of a frozen producer) landing in scratch
+        self._frozen_scratch = []    # where the kernels above the frontier leave the gradients of frozen parameters (never exposed)
         self.fin_name = "mny_bn_bwd_finalize_frozen" if self.frozen else "mny_bn_bwd_finalize"
         self._gs = {v.id: _Grad() for v in g.values}
         self.grad_bufs = []
@@ -744,20 +765,15 @@ class NetPlan:
                 slack[nd.conv + ".weight"] = cp * nd.ins[0].C
                 slack[nd.conv + ".bias"] = cp
         for nd in order:
-            names = []
-            if nd.conv:
-                names.append(nd.conv + ".weight")
-                if nd.bias:
-                    names.append(nd.conv + ".bias")
-            if nd.bn:
-                names += [nd.bn + ".weight", nd.bn + ".bias"]
-            for nm in names:
-                if nm in slots:
-                    continue                     # module applied twice (mbv3_yolo.py:133-134): one slot, two contributions
+            for nm in frontier.node_params(nd):
+                if nm in slots or nm in self.frontier.frozen:
+                    continue                     # module applied twice (mbv3_yolo.py:133-134): one slot, two contributions; a frozen parameter: none
                 n = P[nm].numel()
                 slots[nm] = (off, n)
                 self.grad_params.append(nm)
                 off += (max(n, slack.get(nm, 0)) + 3) // 4 * 4
+        assert self.grad_params == self.frontier.grad_params
+        self._slack = slack
         self.gflat = torch.zeros(off, **self._f32)
         self.gviews = {nm: self.gflat[o:o + n].view(P[nm].shape) for nm, (o, n) in slots.items()}
         self.grad_slots = slots
@@ -785,6 +801,8 @@ class NetPlan:
         """dL/d(loss input) = upstream scale * what the loss call left, padded for the heads whose channel count the GEMMs cannot take."""
         bwd, gs = self.bwd, self._gs
         for hi, o in enumerate(self.loss_outputs):
+            if not self.frontier.needs_grad(o):
+                continue                     # nothing trainable feeds this loss
             dh = self.dheads[hi]
             if o.id in self.head_cp:
                 cp = self.head_cp[o.id]
@@ -807,6 +825,8 @@ class NetPlan:
         for nd in order:
             if nd.op not in ("pw", "pwb") or self._takes_own_sums(nd) or nd.conv in self.wT:
                 continue
+            if not self.frontier.needs_grad(nd.ins[0]) and not self._lr_ok(nd):
+                continue                     # at the frontier: the generic route leaves the data gradient out (the low-rank route runs whole)
             w = self._P[nd.conv + ".weight"]
             oc = self.head_cp.get(nd.out.id, nd.out.C)
             wT = torch.empty(nd.ins[0].C, oc, **self._act)
@@ -833,6 +853,11 @@ class NetPlan:
     def _gv(self, nm):
         """Destination of a parameter gradient.  The first contribution writes the arena slot; a later one (shared
         module) writes a scratch tensor that `_flush_shared()` adds into the slot right after the producing call."""
+        if nm in self.frontier.frozen:       # frozen parameter above the frontier: the kernels run as they do, into scratch
+            p = self._P[nm]
+            buf = torch.empty(max(p.numel(), self._slack.get(nm, 0)), **self._f32)
+            self._frozen_scratch.append(buf)
+            return buf[:p.numel()].view(p.shape)
         if nm not in self._written:
             self._written.add(nm)
             return self.gviews[nm]
@@ -1092,10 +1117,12 @@ class NetPlan:
         self._contribute_kernel(pi, emit, inplace_ok=False)
 
     def _bwd_add(self, nd, G):
-        self._contribute_alias(nd.ins[0], G)
-        if nd.k & 1:
+        need = self.frontier.needs_grad
+        if need(nd.ins[0]):
+            self._contribute_alias(nd.ins[0], G)
+        if nd.k & 1 and need(nd.ins[1]):
             self._contribute_alias(nd.ins[1], G)
-        if nd.k & 2:
+        if nd.k & 2 and need(nd.ins[-1]):
             self._accumulate_into(nd.ins[-1], lambda dst, acc: self.bwd.add(self.K("mny_upsample_bwd"), G, dst, acc, *self._shape(nd.out), self.stream))
 
     def _bwd_mul(self, nd, G):
@@ -1104,14 +1131,18 @@ class NetPlan:
 
         def times(other):
             return lambda out, addend: self.bwd.add(self.K("mny_mul_views_bwd"), G, other[0], other[1], other[2], other[3], addend, out, M, C, self.stream)
-        self._contribute_kernel(nd.ins[0], times(vb))
-        self._contribute_kernel(nd.ins[1], times(va))
+        if self.frontier.needs_grad(nd.ins[0]):
+            self._contribute_kernel(nd.ins[0], times(vb))
+        if self.frontier.needs_grad(nd.ins[1]):
+            self._contribute_kernel(nd.ins[1], times(va))
 
     def _bwd_partadd(self, nd, G):
         av, upv = nd.ins[0], nd.ins[1]
         M = self._rows(nd.out)
-        self._accumulate_into(av, lambda dst, acc: self.bwd.add(self.K("mny_slice_channels"), G, dst, acc, M, av.C, nd.out.C, self.stream))
-        self._accumulate_into(upv, lambda dst, acc: self.bwd.add(self.K("mny_upsample_bwd"), G, dst, acc, *self._shape(nd.out), self.stream))
+        if self.frontier.needs_grad(av):
+            self._accumulate_into(av, lambda dst, acc: self.bwd.add(self.K("mny_slice_channels"), G, dst, acc, M, av.C, nd.out.C, self.stream))
+        if self.frontier.needs_grad(upv):
+            self._accumulate_into(upv, lambda dst, acc: self.bwd.add(self.K("mny_upsample_bwd"), G, dst, acc, *self._shape(nd.out), self.stream))
 
     def _bwd_thin_expand(self, nd, G):
         """thin "expand" unit: BN-backward + wgrad + dgrad from (G, Y, X) in 4 passes, dY never materialised."""
@@ -1352,6 +1383,8 @@ class NetPlan:
             bwd.add_py(self._fork_side, "fork")
         bwd.add(self.K("mny_dw_bwd_weight"), xv[0], xv[1], xv[2], xv[3], dY, dwv_, dws_, N, ish[1], ish[2], C,
                 k, s, self.stream_side if on_side else self.stream, meta=meta)
+        if not self.frontier.needs_grad(i):
+            return                               # at the frontier: nothing upstream takes a gradient
         self._contribute_kernel(i, lambda out, addend: bwd.add(
             self.K("mny_dw_bwd_data"), dY, w, addend, out, N, ish[1], ish[2], C, k, s, self.stream, meta=dict(meta)))
 
@@ -1373,6 +1406,8 @@ class NetPlan:
         bwd.add(K("mny_pw_wgrad"), xv[0], xv[1], xv[2], xv[3], dY, dwv_, db, pws_, M, i.C, oc,
                 self.stream_side if on_side else self.stream,
                 meta=dict(flops=2 * M * i.C * o.C, bytes=eb * (M * i.C + M * o.C) + 4 * i.C * o.C, shape="M%d K%d N%d" % (M, i.C, oc)))
+        if not self.frontier.needs_grad(i):
+            return                               # at the frontier: nothing upstream takes a gradient
         wT = self.wT[nd.conv]                   # filled by the batched transpose at the head of the list
         wT6 = self.wT6.get(nd.conv)             # pre-cut W^T planes: this data gradient takes the six-product bf16 form
         # (bf16 storage: round 2 measured the epilogue's 2-byte loads of the unit's output at what the saved pass cost, 3 281 vs

@@ -133,6 +133,7 @@ class yolo(nn.Module):
         d = self.__dict__.copy()
         d["_plans"], d["_anchor"], d["grad_hook"] = {}, None, None
         d.pop("dp_reducer", None)
+        d.pop("_holders", None)
         return d
 
     # ---- parameters ---------------------------------------------------------------------------
@@ -208,14 +209,46 @@ class yolo(nn.Module):
     # ---- plans --------------------------------------------------------------------------------
     PLAN_BUDGET_FRAC = 0.6        # share of the device's HBM the cached plans may keep resident
 
-    def _plan(self, N, H, W, training, slot=0):
+    def _mode_holders(self):
+        """(parameter holders, BatchNorm modules) by state_dict name, listed once: the module tree never changes after construction."""
+        h = self.__dict__.get("_holders")
+        if h is None:
+            params, bns = [], []
+            for mname, mod in self.named_modules():
+                for pname, par in mod._parameters.items():
+                    if par is not None:
+                        params.append((mname + "." + pname if mname else pname, mod, pname))
+                if isinstance(mod, nn.BatchNorm2d):
+                    bns.append((mname, mod))
+            h = self.__dict__["_holders"] = (params, bns)
+        return h
+
+    def frozen_param_names(self):
+        """Names of the parameters with requires_grad == False."""
+        return tuple(nm for nm, mod, pn in self._mode_holders()[0] if not mod._parameters[pn].requires_grad)
+
+    def bn_eval_names(self):
+        """Names of the BatchNorm modules in eval mode."""
+        return tuple(nm for nm, mod in self._mode_holders()[1] if not mod.training)
+
+    def _plan_key(self, N, H, W, training, slot=0, frozen=(), bn_eval=()):
+        """Cache key of a plan.  `frozen` counts for the plans with a backward list, `bn_eval` for those on batch statistics; with every
+        parameter trainable and every BatchNorm in training mode the key is what it was before either existed."""
+        key = (N, H, W, training) if self.act_dtype == torch.float32 else (N, H, W, training, "bf16")
+        if slot:
+            key = key + ("slot%d" % slot,)
+        if frozen and training in (True, "evalgrad"):
+            key = key + (("frozen",) + tuple(frozen),)
+        if bn_eval and training in (True, "traindet"):
+            key = key + (("bn_eval",) + tuple(bn_eval),)
+        return key
+
+    def _plan(self, N, H, W, training, slot=0, frozen=(), bn_eval=()):
         """`training`: True (loss + backward, batch statistics), False (decode + NMS, running statistics), "traindet" (decode + NMS on BATCH
         statistics with the running-statistics update: `model.train()(images)`, mbv2_yolo.py:158-166 in training mode), "evalloss" (loss on running
         statistics, no statistics update, forward only: `model.eval()(images, targets)` under no_grad) or "evalgrad" (the same with the
         backward list of frozen BatchNorm: `model.eval()(images, targets)` with gradients, mbv2_yolo.py:157)."""
-        key = (N, H, W, training) if self.act_dtype == torch.float32 else (N, H, W, training, "bf16")
-        if slot:
-            key = key + ("slot%d" % slot,)
+        key = self._plan_key(N, H, W, training, slot, frozen, bn_eval)
         p = self._plans.get(key)
         if p is None or p.stale():
             if not torch.cuda.is_available() or self.device.type != "cuda":
@@ -225,7 +258,8 @@ class yolo(nn.Module):
             self._plans.pop(key, None)
             before = torch.cuda.memory_allocated(self.device)
             p = NetPlan(self, N, H, W, training in (True, "evalloss", "evalgrad"), self.act_dtype, bn_batch=(training is True or training == "traindet"),
-                        frozen_bwd=(training == "evalgrad"))
+                        frozen_bwd=(training == "evalgrad"), frozen_params=frozen if training in (True, "evalgrad") else (),
+                        bn_eval=bn_eval if training in (True, "traindet") else ())
             p.resident_bytes = max(torch.cuda.memory_allocated(self.device) - before, 0)
             self._plans[key] = p
             # multi-scale training keeps one plan per size: bound them by resident BYTES (a bs=256/352x352 training plan holds
@@ -244,12 +278,13 @@ class yolo(nn.Module):
 
     MAX_INFLIGHT = 2                               # differentiable forwards of one shape that may await their backward at the same time
 
-    def _grad_plan(self, N, H, W, mode):
+    def _grad_plan(self, N, H, W, mode, frozen=(), bn_eval=()):
         """The plan a differentiable forward runs on: the first one of the shape whose previous step is settled (backward ran, or its graph was
         dropped); all MAX_INFLIGHT busy: the one whose forward is oldest (its pending backward then raises, as a stale step always did)."""
         plans = []
         for slot in range(self.MAX_INFLIGHT):
-            p = self._plan(N, H, W, mode, slot)
+            # (a plain step calls _plan with the five arguments it always had: tests/test_module_cpu.py stands in for it with that signature)
+            p = self._plan(N, H, W, mode, slot, frozen, bn_eval) if (frozen or bn_eval) else self._plan(N, H, W, mode, slot)
             if getattr(p, "inflight_gen", None) is None:
                 return p
             plans.append(p)
@@ -272,24 +307,35 @@ class yolo(nn.Module):
             return self._forward_eval(x)
         if self.has_seg and seg_maps is not None:
             seg_maps = seg_maps.to(device=x.device, dtype=torch.float32)
-        if self.training:
-            plan = self._grad_plan(N, H, W, True)
-            if self._anchor is None or self._anchor.device != x.device:
-                self._anchor = torch.zeros((), device=x.device, requires_grad=True)
-            nbt = [b for k, b in self.named_buffers() if k.endswith("num_batches_tracked")]
-            torch._foreach_add_(nbt, 1)
-            losses, metrics = _TrainStep.apply(x, self._anchor, self, plan, targets, seg_maps if self.has_seg else None)
-        elif torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+        # every BatchNorm module in eval mode under model.train() is model.eval() as far as the losses go: running statistics, no update
+        params, bns = self._mode_holders()
+        bn_eval = self.bn_eval_names() if self.training else ()
+        batch_stats = self.training and len(bn_eval) < len(bns)
+        grad = torch.is_grad_enabled()
+        # A call that owes no backward (grad mode off) is planned like one with every parameter frozen: no backward list, no gradient
+        # arena, and no BatchNorm module on a gradient path for the mode check to refuse.  Parameters with requires_grad == False take
+        # no gradient and the backward list stops at the frontier they leave (frontier.py).
+        frozen = self.frozen_param_names() if grad else tuple(nm for nm, _mod, _pn in params)
+        if batch_stats:
+            plan = self._grad_plan(N, H, W, True, frozen, bn_eval)
+        elif grad and len(frozen) < len(params):
             # model.eval()(images, targets) with gradients — frozen-BatchNorm fine-tuning (mbv2_yolo.py:157 returns differentiable losses in
-            # eval mode): running statistics in the forward, untouched buffers, and a backward in which they are constants
-            plan = self._grad_plan(N, H, W, "evalgrad")
-            if self._anchor is None or self._anchor.device != x.device:
-                self._anchor = torch.zeros((), device=x.device, requires_grad=True)
-            losses, metrics = _TrainStep.apply(x, self._anchor, self, plan, targets, seg_maps if self.has_seg else None)
+            # eval mode): untouched buffers, and a backward in which the statistics are constants
+            plan = self._grad_plan(N, H, W, "evalgrad", frozen)
         else:
             # model.eval()(images, targets) under no_grad — a validation loss: nn.BatchNorm2d normalises with the running statistics and
             # leaves them untouched (mobilenetv2.py:41-84 in eval mode); forward-only plan
             plan = self._plan(N, H, W, "evalloss")
+        if batch_stats:                                   # (the plan is resolved, every refusal included, before any state moves)
+            on = [mod.num_batches_tracked for _nm, mod in bns if mod.training and mod.num_batches_tracked is not None]
+            torch._foreach_add_(on, 1)
+        if plan.bwd is not None:
+            if self._anchor is None or self._anchor.device != x.device:
+                self._anchor = torch.zeros((), device=x.device, requires_grad=True)
+            losses, metrics = _TrainStep.apply(x, self._anchor, self, plan, targets, seg_maps if self.has_seg else None)
+        else:
+            # no backward list — grad mode off, or nothing trainable that a loss depends on: losses without a graph, like torch; on batch
+            # statistics this is still the training forward, statistics update included
             with torch.no_grad():
                 res = plan.forward_train(x, targets, seg_maps if self.has_seg else None).clone()
                 losses, metrics = res[:, 0].contiguous(), res[:, 1:].contiguous()
@@ -315,7 +361,7 @@ class yolo(nn.Module):
         return tuple(out)
 
     def _run_backward(self, plan, g_losses):
-        P = dict(self.named_parameters())
+        P = dict(self.named_parameters())             # (plan.grad_params lists trainable parameters only: a frozen one's .grad is never touched)
         # gradient accumulation (backward twice without zero_grad(set_to_none=True)): keep the old arena
         first = P[plan.grad_params[0]]
         prev = None
@@ -345,9 +391,13 @@ class yolo(nn.Module):
         if self.training:
             # model.train()(images): the reference decodes + runs NMS in any mode (mbv2_yolo.py:158-166); its BatchNorm layers are then in
             # training mode — batch statistics, running statistics and num_batches_tracked updated — and so are these
-            plan = self._plan(N, H, W, "traindet")
-            nbt = [b for k, b in self.named_buffers() if k.endswith("num_batches_tracked")]
-            torch._foreach_add_(nbt, 1)
+            bn_eval = self.bn_eval_names()
+            if len(bn_eval) == len(self._mode_holders()[1]):
+                plan = self._plan(N, H, W, False)                              # every BatchNorm in eval mode: the eval plan
+            else:
+                plan = self._plan(N, H, W, "traindet", 0, (), bn_eval)
+                on = [mod.num_batches_tracked for _nm, mod in self._mode_holders()[1] if mod.training and mod.num_batches_tracked is not None]
+                torch._foreach_add_(on, 1)
         else:
             plan = self._plan(N, H, W, False)
         with torch.no_grad():

@@ -7,15 +7,19 @@ One HIP launch per step updates every parameter (the reference issues ~200 small
 torch's (`state[p] = {"step", "exp_avg", "exp_avg_sq"}`; the two moments are views into flat buffers), so
 `state_dict()` / `load_state_dict()` interoperate with `torch.optim.AdamW` checkpoints.  Parameters whose `.grad` is
 None are skipped exactly like upstream (the seg branch, Q10).  fp32 CUDA(HIP) parameters only; no CPU fallback.
+
+`clip_grad_norm_(model_or_parameters, max_norm)` is `torch.nn.utils.clip_grad_norm_` (L2) in two launches on the same gradients
+and without a host synchronisation (mny_grad_clip).
 """
 import ctypes
 
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, dp
 
 CHUNK = 65536
+_SEG_DT = np.dtype([("g", np.uint64), ("n", np.int64), ("block0", np.int32), ("pad", np.int32)])
 _CHUNK_DT = np.dtype([("p", np.uint64), ("g", np.uint64), ("m", np.uint64), ("v", np.uint64), ("n", np.int32), ("vec4", np.int32)])
 
 
@@ -116,3 +120,51 @@ class AdamW(torch.optim.Optimizer):
                 _lib.call("mny_adamw_step", ctypes.c_void_p(sub["table"].data_ptr()), sub["nchunks"], float(group["lr"]), float(b1), float(b2),
                           float(group["eps"]), float(group["weight_decay"]), sub["t"], st)
         return loss
+
+
+def clip_segment_table(segments):
+    """[(address, floats)] -> (host table of mny_clip_seg rows, total blocks): each segment's blocks follow its predecessor's."""
+    rows, nblocks = [], 0
+    for ptr, n in segments:
+        rows.append((ptr, n, nblocks, 0))
+        nblocks += _lib.query("mny_grad_clip_parts", n)
+    return np.array(rows, dtype=_SEG_DT), nblocks
+
+
+_clip_cache = {}          # device -> (signature, segment table, workspace, out): rebuilt only when a gradient pointer changes
+
+
+def clip_grad_norm_(parameters, max_norm):
+    """`torch.nn.utils.clip_grad_norm_(parameters, max_norm)` with the L2 norm: scales every `.grad` in place by
+    min(1, max_norm / (total_norm + 1e-6)) and returns total_norm as a 0-dim device tensor — two launches (mny_grad_clip), no host
+    synchronisation; a non-finite norm propagates into the gradients as it does upstream.  `parameters`: an iterable of parameters, one
+    parameter, or a module; pending all-reduces of models with data-parallel gradients attached (dp.attach_data_parallel) are waited for
+    first, in every one of these forms, so the AVERAGED gradients are clipped.  The gradients may be the model's arena views or any other contiguous fp32 CUDA(HIP) tensors; each
+    one is a segment of its own, so the padding between arena slots never enters the norm."""
+    dp.wait_pending()               # averaged gradients, whichever way the parameters were handed over (no reducer attached: nothing to wait for)
+    if isinstance(parameters, torch.nn.Module):
+        parameters = parameters.parameters()
+    elif isinstance(parameters, torch.Tensor):
+        parameters = [parameters]
+    grads = [p.grad for p in parameters if p.grad is not None]
+    if not grads:
+        return torch.tensor(0.0)
+    for g in grads:
+        if not (g.is_cuda and g.dtype == torch.float32 and g.is_contiguous()):
+            raise _lib.MnyError("clip_grad_norm_ needs contiguous fp32 CUDA(HIP) gradients (got %s on %s) — there is no CPU fallback" % (g.dtype, g.device))
+    dev = grads[0].device
+    if any(g.device != dev for g in grads):
+        raise _lib.MnyError("clip_grad_norm_: gradients on several devices")
+    sig = tuple((g.data_ptr(), g.numel()) for g in grads if g.numel())
+    if not sig:
+        return torch.zeros((), device=dev)
+    cached = _clip_cache.get(dev)
+    if cached is None or cached[0] != sig:
+        host, nblocks = clip_segment_table(sig)
+        table = torch.from_numpy(host.view(np.uint8).reshape(-1)).to(dev)
+        cached = _clip_cache[dev] = (sig, table, torch.empty(nblocks, device=dev, dtype=torch.float64), torch.empty(2, device=dev, dtype=torch.float32), nblocks)
+    _, table, ws, out, nblocks = cached
+    with torch.cuda.device(dev):
+        _lib.call("mny_grad_clip", ctypes.c_void_p(table.data_ptr()), len(sig), nblocks, float(max_norm), ctypes.c_void_p(ws.data_ptr()),
+                  ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+        return out[0].clone()               # (the two result floats are reused by the next call)

@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """How far is every parameter gradient of a train step from the CPU oracle's, as a TENSOR (not only its norm)?
-    python tools/grad_direction.py [bs ...]      (default 8 64; 256 needs ~60 GB of host memory)
+    python tools/grad_direction.py [--freeze-backbone] [--bn-eval] [bs ...]      (default 8 64; 256 needs ~60 GB of host memory)
+--freeze-backbone: requires_grad_(False) on every backbone parameter of both models; --bn-eval: also backbone.eval() (the fine-tuning
+configuration of tests/test_gpu_finetune.py).
 Prints, per batch size, the worst and the five largest  ||g - g_ref|| / ||g_ref||  and  1 - cos(g, g_ref)  over the 202 tensors —
 the measurement behind the direction bounds of tests/test_gpu_net.py."""
 import os
@@ -14,13 +16,21 @@ from oracle import net_ref, procedural  # noqa: E402
 
 def main():
     from mobilenet_yolo_pytorch_amd import yolo
-    sizes = [int(v) for v in sys.argv[1:]] or [8, 64]
+    flags = {a for a in sys.argv[1:] if a.startswith("--")}
+    assert flags <= {"--freeze-backbone", "--bn-eval"}, flags
+    sizes = [int(v) for v in sys.argv[1:] if not v.startswith("--")] or [8, 64]
     for bs in sizes:
         torch.manual_seed(0)
         m = yolo(procedural.VOC_CONFIG)
         procedural.fill_state_dict_(m)
         m = m.cuda().train()
         ref = procedural.fill_state_dict_(net_ref.RefYolo(procedural.VOC_CONFIG)).train()
+        for net in (m, ref):
+            if "--freeze-backbone" in flags:
+                for p in net.backbone.parameters():
+                    p.requires_grad_(False)
+            if "--bn-eval" in flags:
+                net.backbone.eval()
         x = procedural.images(bs, 352, 352, seed=5 if bs >= 64 else 3)
         tg = procedural.targets(bs, seed=6 if bs >= 64 else 4, empty_every=5 if bs >= 64 else 4)
         res = m(x.cuda(), tg)
