@@ -438,7 +438,10 @@ int mny_pw_dgrad_bnred_w6(const float* dy, const void* wT6, const float* addend,
 /* ---- which kernel family a pointwise-conv call takes (pure host query; tests and tools/plan_stats.py use it to PROVE that a
  * plan compared with the oracle contains the kernels the benchmark runs) ----------------------------------------------------------
  * op: 0 = mny_pw_fwd (forward / plain data gradient of nn.Conv2d(K,Nc,1), mobilenetv2.py:63-85), 1 = mny_pw_dgrad_bnred[_add],
- * 2 = mny_pw_wgrad (no bias gradient).  bf16: the storage type of the plan (0 = fp32).  Returns one of MNY_ROUTE_*. */
+ * 2 = mny_pw_wgrad (no bias gradient).  bf16: the storage type of the plan (0 = fp32).  Returns one of MNY_ROUTE_*: the launchers' own
+ * rule (the function every *_parts / *_splits / *_supported query asks as well) evaluated for a call with a plain view — no input
+ * view, bias, addend or bias gradient.  After such a call mny_pw_last_route returns the same value; a call behind an h-swish view or
+ * with a bias (gradient) can take another family. */
 enum {
     MNY_ROUTE_TILE_V1 = 0,      /* register-staged tile kernels (unaligned channel counts) */
     MNY_ROUTE_DMA_F32 = 1,      /* LDS-DMA tile kernel, fp32 MFMA (or the bf16 MFMA with bf16 storage) */
@@ -448,8 +451,8 @@ enum {
     MNY_ROUTE_WGRAD_STREAM = 5, /* barrier-free stream weight-gradient kernel (pwwgs.hip) */
     MNY_ROUTE_WAVE16 = 6        /* bf16 storage, K <= 48 at >= 131072 pixels: a wave per 16 pixels on the bf16 matrix cores (gate.hip pwt_fwd_kernel) */
 };
-int mny_pw_route(int op, int bf16, int64_t M, int K, int Nc);   /* PREDICTION for a plain view (no h-swish input, no bias gradient) */
-/* the family the LAST pointwise-conv call of the calling thread actually took (recorded by the dispatchers where they decide; -1 before
+int mny_pw_route(int op, int bf16, int64_t M, int K, int Nc);   /* the family of a plain-view call (no h-swish input, no bias gradient) */
+/* the family the LAST pointwise-conv call of the calling thread actually took (every launcher records the route it acted on; -1 before
  * the first call).  engine.py records it for every call of a plan's first replay: NetPlan.kernel_routes() reports what ran. */
 int mny_pw_last_route(void);
 

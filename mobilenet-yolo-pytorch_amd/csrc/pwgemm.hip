@@ -982,21 +982,31 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((X6 == 3 &&
 }
 
 typedef void (*Nt2Kernel)(Gemm2Args);
-static Nt2Kernel nt2_kernel(int TN, int XF, int BF = 0, int X6 = 0) {
-    if (X6 == 3 && !BF) {                           // pre-cut weight planes (mny_pw_fwd_w6)
-#define MNY_K6(T) (XF == 0 ? (Nt2Kernel)pw_gemm_nt_dma_kernel<T, 0, 0, 0, 3> : XF == 1 ? (Nt2Kernel)pw_gemm_nt_dma_kernel<T, 1, 0, 0, 3> : (Nt2Kernel)pw_gemm_nt_dma_kernel<T, 2, 0, 0, 3>)
-        switch (TN) { case 1: return MNY_K6(1); case 2: return MNY_K6(2); case 3: return MNY_K6(3); case 4: return MNY_K6(4); default: return MNY_K6(5); }
-#undef MNY_K6
+// THE table of pw_gemm_nt_dma_kernel instantiations: what is not named here is not compiled (one more live register broke <3,0,1,2>)
+static constexpr int nt2_key(int TN, int XF, int BF, int RED, int X6, int RB) { return ((((TN * 3 + XF) * 2 + BF) * 3 + RED) * 4 + X6) * 2 + RB; }
+static Nt2Kernel nt2_kernel(int TN, int XF, int BF = 0, int RED = 0, int X6 = 0, int RB = 0) {      // nullptr: no such kernel
+#define MNY_K(T, XF_, BF_, RED_, X6_, RB_) case nt2_key(T, XF_, BF_, RED_, X6_, RB_): return (Nt2Kernel)pw_gemm_nt_dma_kernel<T, XF_, BF_, RED_, X6_, RB_>;
+#define MNY_FWD(T, BF_, X6_) MNY_K(T, 0, BF_, 0, X6_, 0) MNY_K(T, 1, BF_, 0, X6_, 0) MNY_K(T, 2, BF_, 0, X6_, 0)      // no view, linear / clamp view, h-swish view
+#define MNY_RED(T, RED_) MNY_K(T, 0, 0, RED_, 0, 0) MNY_K(T, 0, 0, RED_, 1, 0) MNY_K(T, 0, 1, RED_, 0, 0)           // fp32 MFMA, six-product, bf16 storage
+#define MNY_FIX(T) MNY_K(T, 0, 0, 2, 0, 1) MNY_K(T, 0, 0, 2, 1, 1) MNY_K(T, 1, 0, 2, 0, 1) MNY_K(T, 1, 0, 2, 1, 1)
+#define MNY_TN5(M_, ...) M_(1, __VA_ARGS__) M_(2, __VA_ARGS__) M_(3, __VA_ARGS__) M_(4, __VA_ARGS__) M_(5, __VA_ARGS__)
+    switch (nt2_key(TN, XF, BF, RED, X6, RB)) {
+        // forward / plain data gradient, column tiles of 32 .. 160: fp32 MFMA, six-product (X6 = 1), pre-cut weight planes (X6 = 3), bf16 storage
+        MNY_TN5(MNY_FWD, 0, 0) MNY_TN5(MNY_FWD, 0, 1) MNY_TN5(MNY_FWD, 0, 3) MNY_TN5(MNY_FWD, 1, 0)
+        // data gradient + BatchNorm sums (RED = 1; = 2: with an addend — own instantiations: the addend loads cost the TN = 4 variant registers),
+        // column tiles of <= 128 (kRedMaxTn); on weight planes the addend form stops at 96
+        MNY_RED(1, 1) MNY_RED(2, 1) MNY_RED(3, 1) MNY_RED(4, 1) MNY_RED(1, 2) MNY_RED(2, 2) MNY_RED(3, 2) MNY_RED(4, 2)
+        MNY_K(1, 0, 0, 1, 3, 0) MNY_K(2, 0, 0, 1, 3, 0) MNY_K(3, 0, 0, 1, 3, 0) MNY_K(4, 0, 0, 1, 3, 0)
+        MNY_K(1, 0, 0, 2, 3, 0) MNY_K(2, 0, 0, 2, 3, 0) MNY_K(3, 0, 0, 2, 3, 0)
+        // low-rank fix with a reduction target (RB = 1: the bias row r), column tiles of <= 96
+        MNY_FIX(1) MNY_FIX(2) MNY_FIX(3)
     }
-    if (X6 && !BF) {
-#define MNY_K6(T) (XF == 0 ? (Nt2Kernel)pw_gemm_nt_dma_kernel<T, 0, 0, 0, 1> : XF == 1 ? (Nt2Kernel)pw_gemm_nt_dma_kernel<T, 1, 0, 0, 1> : (Nt2Kernel)pw_gemm_nt_dma_kernel<T, 2, 0, 0, 1>)
-        switch (TN) { case 1: return MNY_K6(1); case 2: return MNY_K6(2); case 3: return MNY_K6(3); case 4: return MNY_K6(4); default: return MNY_K6(5); }
-#undef MNY_K6
-    }
-#define MNY_K(T) (BF ? (XF == 0 ? (Nt2Kernel)pw_gemm_nt_dma_kernel<T, 0, 1> : XF == 1 ? (Nt2Kernel)pw_gemm_nt_dma_kernel<T, 1, 1> : (Nt2Kernel)pw_gemm_nt_dma_kernel<T, 2, 1>) \
-                     : (XF == 0 ? (Nt2Kernel)pw_gemm_nt_dma_kernel<T, 0, 0> : XF == 1 ? (Nt2Kernel)pw_gemm_nt_dma_kernel<T, 1, 0> : (Nt2Kernel)pw_gemm_nt_dma_kernel<T, 2, 0>))
-    switch (TN) { case 1: return MNY_K(1); case 2: return MNY_K(2); case 3: return MNY_K(3); case 4: return MNY_K(4); default: return MNY_K(5); }
+#undef MNY_TN5
+#undef MNY_FIX
+#undef MNY_RED
+#undef MNY_FWD
 #undef MNY_K
+    return nullptr;
 }
 
 // fp32 GEMMs whose matrix-core time exceeds their HBM time take the six-product bf16 form (MNY_X6=0: never, =1: always, for A/B runs)
@@ -2674,20 +2684,169 @@ int pw_bnbwd_finalize_launch(const float* partials, int nparts, float* red, cons
 using namespace mny;
 static thread_local int g_pw_route = -1;        // kernel family of this thread's last pointwise-conv call (mny_pw_last_route below)
 
-extern "C" int mny_pw_stat_parts(int64_t M, int K, int Nc) {
-    if (M <= 0 || K <= 0 || Nc <= 0) return MNY_EINVAL;
-    if (pw_thin_ok(0, 0, M, K, Nc)) return pw_thin_parts(M, K, Nc, 0);
-    if (pw_wide_ok(M, K, Nc, false)) return pw_wide_parts(M, K, Nc, false) + ((M & 31) ? nt2_plan(M & 31, K, Nc, true).gx : 0);      // + the last M % 32 rows
-    if ((K & 3) == 0 && !sw(SW_GEMM_V1)) return nt2_plan(M, K, Nc, true).gx;
-    return nt_plan(M, K, Nc).gx;
+// ---- which kernel a pointwise-conv call takes ------------------------------------------------------------------------------------------
+// One route function per operation: the complete description of a call in, the decision out.  The launchers act on it, and every *_parts /
+// *_splits / *_supported / *_ws_floats query, mny_pw_w6_supported and mny_pw_route ask the same function about the PLAIN call (no view, no
+// bias, no addend) — so a query cannot count other rows than the launcher's kernel writes.  The kernel families' own predicates (pw_thin_ok,
+// pw_wide_ok, pwt_ok, pw_wgs_ok, pw_wide_fix_ok), the MNY_GEMM_V1 / MNY_WGRAD_V1 switches and the channel-alignment tests appear here only.
+struct PwRoute {
+    int family = MNY_ROUTE_TILE_V1;     // MNY_ROUTE_*
+    const char* why = nullptr;          // NULL: supported; else what keeps the call off this entry point
+    int parts = MNY_EINVAL;             // partial rows (weight gradient: splits) the call writes
+    bool as_counted = true;             // the plain call takes the same family — and rows are a function of family and shape: what the query counted holds
+    int64_t Mf = 0;                     // wide family: the rows on whole 32-row tiles, wide_parts partial rows; the last M - Mf rows (one more partial
+    int wide_parts = 0;                 //   row) follow on the LDS-DMA kernel by `p2`
+    int x6 = 0;                         // LDS-DMA families, the X6 of the kernel: 0 = fp32 / bf16 MFMA, 1 = six-product form, 3 = on pre-cut weight planes
+    Nt2Plan p2{};                       // LDS-DMA families (and the wide family's last rows)
+    size_t lds = 0;                     //   their dynamic LDS
+    WgPlan wg{};                        // weight gradient, tile kernels
+};
+
+// Pre-cut weight planes pay where the matrix pipe is the bound.  Round 2: a stage of B grew from 64 to 96 bytes per row, which cost the mid-size
+// shapes their third resident workgroup (7-18 % faster from ~60 FLOP per byte up, 10-30 % slower below ~40).  Round 3: the plane ring is two
+// slots deep (the A ring stays at three), the LDS footprint equals the plain mode's and the threshold moved down to 30 FLOP per byte
+// (same-box A/B per shape: K576 N96 -11 %, K384 N96 -10 %, the 75-channel heads -9..-11 %, K384 N64 (27 FLOP per byte) +0..+7 % -> 30, was 50)
+static bool w6_pays(int K, int Nc) {
+    constexpr double min_ai = 30.0;
+    return !sw(SW_NO_W6) && 2.0 * K * Nc / (4.0 * (K + Nc)) >= min_ai;
 }
-extern "C" int mny_pw_stat_parts_bf16(int64_t M, int K, int Nc) {
-    if (M <= 0 || K <= 0 || Nc <= 0) return MNY_EINVAL;
-    if (pwt_ok(M, K, Nc, MNY_ACT_NONE, false)) return pwt_parts(M);
-    if (pw_thin_ok(1, 0, M, K, Nc)) return pw_thin_parts(M, K, Nc, 0);
-    if ((K & 7) == 0 && !sw(SW_GEMM_V1)) return nt2_plan(M, K, Nc, true, 1).gx;
-    return nt_plan(M, K, Nc).gx;
+
+// forward / plain data gradient (mny_pw_fwd, _bf16, _w6).  view: the input is read through in_scale / in_shift; planes: the weight is pre-cut (fp32)
+static PwRoute pw_fwd_route(int bf, int64_t M, int K, int Nc, int in_act, bool view, bool bias, bool addend, bool planes) {
+    PwRoute r;
+    if (M <= 0 || K <= 0 || Nc <= 0) { r.why = "empty problem"; return r; }
+    const bool v1 = sw(SW_GEMM_V1);   // A/B switch for profiling
+    const bool thin = pw_thin_ok(bf, 0, M, K, Nc);                    // short reduction: vector-ALU stream kernel (pwthin.hip)
+    const bool wide = !bf && !thin && pw_wide_ok(M, K, Nc, false);    // short reduction, wide output: barrier-free matrix-core kernel (pwwide.hip)
+    auto family = [&](int act, bool has_bias, bool has_addend) {
+        if (bf && pwt_ok(M, K, Nc, act, has_bias)) return MNY_ROUTE_WAVE16;      // K <= 48 at a large pixel count: a wave per 16 pixels on the bf16 matrix cores (gate.hip)
+        if (thin) return MNY_ROUTE_THIN;
+        if (wide && !has_bias && !has_addend && act != MNY_ACT_HSIGMOID) return MNY_ROUTE_WIDE;      // (that kernel knows no bias, addend or h-sigmoid view)
+        if ((K & (bf ? 7 : 3)) || v1) return MNY_ROUTE_TILE_V1;                  // the LDS-DMA pipeline reads 16-B aligned input rows
+        return !bf && nt_x6(M, K, Nc) ? MNY_ROUTE_DMA_X6 : MNY_ROUTE_DMA_F32;
+    };
+    r.family = family(in_act, bias, addend);
+    const int plain = in_act == MNY_ACT_NONE && !bias && !addend ? r.family : family(MNY_ACT_NONE, false, false);
+    r.as_counted = r.family == plain;
+    // pre-cut planes: one set serves a weight's forward and (transposed) its data gradient with sums — one rule for both
+    if (planes && (bf || plain != MNY_ROUTE_DMA_X6 || pw_wide_ok(M, K, Nc, true) || !w6_pays(K, Nc))) r.why = "no pre-cut weight planes for this problem (mny_pw_w6_supported)";
+    const bool xf = view || in_act != MNY_ACT_NONE;
+    switch (r.family) {
+        case MNY_ROUTE_WAVE16: r.parts = pwt_parts(M); return r;
+        case MNY_ROUTE_THIN: r.parts = pw_thin_parts(M, K, Nc, 0); return r;
+        case MNY_ROUTE_TILE_V1: r.parts = nt_plan(M, K, Nc).gx; return r;
+        case MNY_ROUTE_WIDE:
+            r.Mf = M & ~(int64_t)31;
+            r.parts = r.wide_parts = pw_wide_parts(M, K, Nc, false);
+            if (r.Mf == M) return r;
+            r.p2 = nt2_plan(M - r.Mf, K, Nc, xf);
+            r.x6 = nt_x6(M, K, Nc);
+            r.parts += r.p2.gx;
+            break;
+        default:
+            r.p2 = nt2_plan(M, K, Nc, xf, bf);
+            r.x6 = r.family == MNY_ROUTE_DMA_X6;
+            r.parts = r.p2.gx;
+    }
+    r.lds = r.p2.lds;
+    size_t lds_max = 64 * 1024;
+    if (planes) {
+        r.x6 = 3;
+#if MNY_W6_SWP
+        // software-pipelined form: three-slot A ring + THREE-slot plane ring (24 + 9 TN KB) + the scale / shift cache; else three-slot A ring +
+        // two-slot plane ring = the plain mode's three-slot (A + fp32 B) ring, to the byte
+        r.lds = (size_t)(3 * BM * 16 + 3 * 32 * r.p2.TN * 24) * sizeof(float) + (xf ? 2 * cdiv(K, 16) * 16 * sizeof(float) : 0);
+#endif
+        lds_max = 96 * 1024;
+    }
+    if (!r.why && r.lds > lds_max) r.why = "K too large for the LDS scale cache";
+    return r;
 }
+
+// data gradient + the BatchNorm-backward sums of the unit it feeds (mny_pw_dgrad_bnred, _add, _bf16, _w6).  The reduction epilogue holds four more
+// per-column constants and a group of loads: the 160-column tile (TN = 5) spills with it
+constexpr int kRedMaxTn = 4;
+static PwRoute pw_dgrad_bnred_route(int bf, int64_t M, int K, int Nc, int act, bool addend, bool planes) {
+    PwRoute r;
+    if (M <= 0 || K <= 0 || Nc <= 0 || (K & (bf ? 7 : 3))) { r.why = "empty problem, or dy rows that are not 16-byte aligned"; return r; }
+    const bool v1 = sw(SW_GEMM_V1), thin32 = pw_thin_ok(0, 1, M, K, Nc), wide = pw_wide_ok(M, K, Nc, true);
+    r.x6 = !bf && nt_x6(M, K, Nc);                            // (the six-product bf16 form exists for fp32 operands only)
+    bool tile = false;
+    if (bf && pwt_ok(M, K, Nc, MNY_ACT_NONE, false)) {        // K <= 48 at a large pixel count: a wave per 16 pixels (gate.hip)
+        r.family = MNY_ROUTE_WAVE16;
+        r.parts = pwt_parts(M);
+    } else if (bf ? pw_thin_ok(1, 1, M, K, Nc) : thin32) {
+        r.family = MNY_ROUTE_THIN;
+        r.parts = pw_thin_parts(M, K, Nc, 1);
+    } else if (!bf && wide) {       // whole 32-row tiles on the barrier-free kernel, the last M % 32 rows on the LDS-DMA kernel (one more partial row)
+        r.family = MNY_ROUTE_WIDE;
+        r.Mf = M & ~(int64_t)31;
+        r.parts = r.wide_parts = pw_wide_parts(M, K, Nc, true);
+        if (r.Mf != M) {
+            r.p2 = nt2_plan(M - r.Mf, K, Nc, false, 0, kRedMaxTn);
+            r.parts += r.p2.gx;
+        }
+    } else {
+        // (MNY_GEMM_V1: the first generation takes no sums — unsupported below; the plain data gradient that runs instead takes those kernels)
+        r.family = v1 ? MNY_ROUTE_TILE_V1 : r.x6 ? MNY_ROUTE_DMA_X6 : MNY_ROUTE_DMA_F32;
+        r.p2 = nt2_plan(M, K, Nc, false, bf, kRedMaxTn);
+        r.parts = r.p2.gx;
+        tile = true;
+    }
+    r.lds = r.p2.lds;
+    if (act < MNY_ACT_NONE || act > MNY_ACT_HSIGMOID) r.why = "unknown activation";
+    else if (v1) r.why = "MNY_GEMM_V1 is set";
+    else if (K >= 512 && Nc >= 512) r.why = "matrix-pipe-bound: the reduce pass it would save is cheaper than the longer epilogue";
+    // (the next two are the fp32 kernels' limits, answered for either storage type: bf16 plans keep the separate reduce pass on the same units)
+    else if (thin32 && act == MNY_ACT_HSIGMOID) r.why = "the short-reduction kernel knows the clamp family and h-swish (what units use)";
+    else if (wide && act >= MNY_ACT_HSWISH) r.why = "the wide-output kernel's reduction form knows the clamp family (its h-swish builds spill)";
+    // the addend variant exists for column tiles of <= 96 (TN <= 3: the 128-column tile has no registers left for the addend loads)
+    else if (addend && tile && r.p2.TN > 3) r.why = "the addend form needs a column tile of <= 96 (mny_pw_dgrad_bnred_add_supported)";
+    else if (planes && (bf || r.family != MNY_ROUTE_DMA_X6 || pw_wide_ok(M, K, Nc, false) || !w6_pays(K, Nc))) r.why = "no pre-cut weight planes for this problem (mny_pw_w6_supported)";
+    else if (r.lds > (size_t)(planes ? 96 : 64) * 1024) r.why = "K too large";
+    if (planes) r.x6 = 3;
+    return r;
+}
+
+// low-rank fix (mny_pw_lr_fix): red = a call WITH a reduction target, the only one that writes partial rows
+static PwRoute pw_lr_fix_route(int64_t M, int K, int r_act, bool red, bool view) {
+    PwRoute r;
+    if (M <= 0 || K <= 0 || (K & 3)) { r.why = "empty problem, or rows that are not 16-byte aligned"; return r; }
+    if (red && pw_wide_fix_ok(M, K) && r_act < MNY_ACT_HSWISH) {            // K = 64 / 96 at whole 32-row tiles: the barrier-free kernel of pwwide.hip
+        r.family = MNY_ROUTE_WIDE;
+        r.parts = pw_wide_fix_parts(M, K);
+        return r;
+    }
+    r.p2 = nt2_plan(M, K, K, view, 0, 3);                                   // always column tiles of <= 96 (the addend form's limit)
+    r.lds = r.p2.lds;
+    r.x6 = nt_x6(M, K, K);
+    r.family = r.x6 ? MNY_ROUTE_DMA_X6 : MNY_ROUTE_DMA_F32;
+    r.parts = r.p2.gx;
+    if (r.lds > 64 * 1024) r.why = "K too large";
+    return r;
+}
+
+// weight gradient (mny_pw_wgrad, _bf16); parts = the splits of the partial rows [splits][Nc][K]
+static PwRoute pw_wgrad_route(int bf, int64_t M, int K, int Nc, int in_act, bool bias_grad) {
+    PwRoute r;
+    if (M <= 0 || K <= 0 || Nc <= 0) { r.why = "empty problem"; return r; }
+    if (!bf && pw_wgs_ok(M, K, Nc) && !bias_grad) {        // narrow-sided shape: barrier-free stream kernel (pwwgs.hip)
+        r.family = MNY_ROUTE_WGRAD_STREAM;
+        r.parts = pw_wgs_splits(M, K, Nc);
+        return r;
+    }
+    // the LDS-DMA kernels read raw 16-B chunks: aligned rows only; the fp32 one has no h-swish view
+    const int al = bf ? 7 : 3;
+    const bool dma = (Nc & al) == 0 && (K & al) == 0 && !sw(SW_WGRAD_V1) && (bf || in_act != MNY_ACT_HSWISH);
+    r.x6 = !bf && dma && nt_x6(M, K, Nc);
+    r.family = !dma ? MNY_ROUTE_TILE_V1 : r.x6 ? MNY_ROUTE_DMA_X6 : MNY_ROUTE_DMA_F32;
+    r.wg = wg_plan(M, K, Nc, bf, !bf && dma);
+    r.parts = r.wg.splits;
+    return r;
+}
+
+extern "C" int mny_pw_stat_parts(int64_t M, int K, int Nc) { return pw_fwd_route(0, M, K, Nc, MNY_ACT_NONE, false, false, false, false).parts; }
+extern "C" int mny_pw_stat_parts_bf16(int64_t M, int K, int Nc) { return pw_fwd_route(1, M, K, Nc, MNY_ACT_NONE, false, false, false, false).parts; }
 
 // register-staged NT kernel (any K, any storage type)
 template <typename T>
@@ -2716,145 +2875,111 @@ static int pw_fwd_v1(const T* x, const float* in_scale, const float* in_shift, i
     return check_launch("pw_gemm_nt_kernel");
 }
 
+// an LDS-DMA launch as its route planned it
+static int nt2_launch(const PwRoute& r, int XF, int BF, int RED, int RB, const Gemm2Args& g, hipStream_t st, const char* what) {
+    const Nt2Kernel k = nt2_kernel(r.p2.TN, XF, BF, RED, r.x6, RB);
+    if (!k) {
+        set_error("%s: no kernel for a %d-column tile", what, 32 * r.p2.TN); return MNY_EUNSUPPORTED;
+    }
+    nt2_allow_lds(k, r.lds);
+    hipLaunchKernelGGL(k, dim3(r.p2.grid), dim3(256), r.lds, st, g);
+    return check_launch(what);
+}
+
+template <int BF>
+static int pw_fwd_impl(const void* x, const float* in_scale, const float* in_shift, int in_act, const void* w, const float* bias, const void* addend,
+                       void* y, float* stats, int64_t M, int K, int Nc, void* stream, bool planes = false) {
+    using T = typename std::conditional<BF != 0, bf16_t, float>::type;
+    MNY_REQUIRE(x && w && y, "pw_fwd: null pointer");
+    MNY_REQUIRE(!(stats && bias), "pw_fwd: stats and bias are mutually exclusive");
+    const PwRoute r = pw_fwd_route(BF, M, K, Nc, in_act, in_scale != nullptr, bias != nullptr, addend != nullptr, planes);
+    MNY_REQUIRE(!r.why, "pw_fwd: M=%lld K=%d N=%d: %s", (long long)M, K, Nc, r.why);
+    // mny_pw_stat_parts[_bf16] sizes the caller's partial rows from (M, K, Nc) alone: a view / bias / addend that moves the call to another kernel
+    // family than the query assumed would write a different number of rows than mny_bn_finalize sums — refuse it instead
+    MNY_REQUIRE(!stats || r.as_counted, "pw_fwd: statistics with in_act=%d%s%s at M=%lld K=%d N=%d take another kernel family than mny_pw_stat_parts%s counted rows for",
+                in_act, bias ? ", a bias" : "", addend ? ", an addend" : "", (long long)M, K, Nc, BF ? "_bf16" : "");
+    g_pw_route = r.family;
+    hipStream_t st = (hipStream_t)stream;
+    switch (r.family) {
+        case MNY_ROUTE_WAVE16: return pwt_launch(x, in_scale, in_shift, in_act, w, addend, y, stats, M, K, Nc, st);
+        case MNY_ROUTE_THIN:
+            return pw_thin_launch(BF, x, in_scale, in_shift, in_act, w, bias, addend, y, stats, M, K, Nc, 0, nullptr, nullptr, nullptr, nullptr, nullptr, 0, st);
+        case MNY_ROUTE_TILE_V1: return pw_fwd_v1<T>((const T*)x, in_scale, in_shift, in_act, (const T*)w, bias, (const T*)addend, (T*)y, stats, M, K, Nc, st);
+        case MNY_ROUTE_WIDE: {      // fp32: whole 32-row tiles; the last M % 32 rows follow below
+            const int rc = pw_wide_launch((const float*)x, in_scale, in_shift, in_act, (const float*)w, (float*)y, stats, r.Mf, K, Nc, nullptr, nullptr, nullptr, nullptr,
+                                          nullptr, 0, nullptr, st);
+            if (rc != 0 || r.Mf == M) return rc;
+            if (stats) stats += (int64_t)r.wide_parts * 2 * Nc;
+            x = (const float*)x + r.Mf * K; y = (float*)y + r.Mf * Nc; M -= r.Mf;
+        }
+    }
+    Gemm2Args g{x, in_scale, in_shift, in_act, w, bias, addend, y, stats, M, K, Nc, r.p2.m_tiles, r.p2.tiles_per_block, r.p2.gx, r.p2.n_tiles,
+                nullptr, nullptr, nullptr, nullptr, nullptr, 0};
+    const int XF = !in_scale && in_act == MNY_ACT_NONE ? 0 : (in_act == MNY_ACT_HSWISH ? 2 : 1);
+    return nt2_launch(r, XF, BF, 0, 0, g, st, "pw_gemm_nt_dma_kernel");
+}
 extern "C" int mny_pw_fwd(const float* x, const float* in_scale, const float* in_shift, int in_act, const float* w,
                           const float* bias, const float* addend, float* y, float* stats, int64_t M, int K, int Nc,
                           void* stream) {
-    MNY_REQUIRE(x && w && y, "pw_fwd: null pointer");
-    MNY_REQUIRE(M > 0 && K > 0 && Nc > 0, "pw_fwd: empty problem");
-    MNY_REQUIRE(!(stats && bias), "pw_fwd: stats and bias are mutually exclusive");
-    hipStream_t st = (hipStream_t)stream;
-    const bool xf = in_scale != nullptr || in_act != MNY_ACT_NONE;
-    const bool force_v1 = sw(SW_GEMM_V1);   // A/B switch for profiling
-    if (pw_thin_ok(0, 0, M, K, Nc)) {                      // short reduction: vector-ALU stream kernel (pwthin.hip)
-        g_pw_route = MNY_ROUTE_THIN;
-        return pw_thin_launch(0, x, in_scale, in_shift, in_act, w, bias, addend, y, stats, M, K, Nc, 0, nullptr, nullptr, nullptr, nullptr, nullptr, 0, st);
-    }
-    bool took_wide = false;
-    if (pw_wide_ok(M, K, Nc, false)) {              // short reduction, wide output: barrier-free matrix-core kernel (pwwide.hip)
-        if (!bias && !addend && in_act != MNY_ACT_HSIGMOID) {
-            const int64_t Mf = M & ~(int64_t)31;    // it takes whole 32-row tiles; the last M % 32 rows follow below (one more partial row)
-            g_pw_route = MNY_ROUTE_WIDE;
-            took_wide = true;
-            const int rc = pw_wide_launch(x, in_scale, in_shift, in_act, w, y, stats, Mf, K, Nc, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, st);
-            if (rc != 0 || Mf == M) return rc;
-            if (stats) stats += (int64_t)pw_wide_parts(M, K, Nc, false) * 2 * Nc;
-            x += Mf * K; y += Mf * Nc; M -= Mf;
-        } else {
-            MNY_REQUIRE(!stats, "pw_fwd: statistics with a bias / addend / h-sigmoid input on a wide-kernel shape");   // (its partial rows follow mny_pw_stat_parts)
-        }
-    }
-    if ((K & 3) == 0 && !force_v1) {                // LDS-DMA pipeline (v2): 16-B aligned input rows
-        Nt2Plan p2 = nt2_plan(M, K, Nc, xf);
-        MNY_REQUIRE(p2.lds <= 64 * 1024, "pw_fwd: K=%d too large for the LDS scale cache", K);
-        Gemm2Args g{x, in_scale, in_shift, in_act, w, bias, addend, y, stats, M, K, Nc, p2.m_tiles, p2.tiles_per_block, p2.gx, p2.n_tiles,
-                    nullptr, nullptr, nullptr, nullptr, nullptr, 0};
-        dim3 grid2(p2.grid), block2(256);
-        const int XF = !xf ? 0 : (in_act == MNY_ACT_HSWISH ? 2 : 1);
-        if (!took_wide) g_pw_route = nt_x6(M, K, Nc) ? MNY_ROUTE_DMA_X6 : MNY_ROUTE_DMA_F32;     // (the last M % 32 rows of a wide-kernel call stay "wide")
-        hipLaunchKernelGGL(nt2_kernel(p2.TN, XF, 0, nt_x6(M, K, Nc)), grid2, block2, p2.lds, st, g);
-        return check_launch("pw_gemm_nt_dma_kernel");
-    }
-    if (!took_wide) g_pw_route = MNY_ROUTE_TILE_V1;
-    return pw_fwd_v1<float>(x, in_scale, in_shift, in_act, w, bias, addend, y, stats, M, K, Nc, st);
+    return pw_fwd_impl<0>(x, in_scale, in_shift, in_act, w, bias, addend, y, stats, M, K, Nc, stream);
+}
+extern "C" int mny_pw_fwd_bf16(const void* x, const float* in_scale, const float* in_shift, int in_act, const void* w,
+                               const float* bias, const void* addend, void* y, float* stats, int64_t M, int K, int Nc,
+                               void* stream) {
+    return pw_fwd_impl<1>(x, in_scale, in_shift, in_act, w, bias, addend, y, stats, M, K, Nc, stream);
 }
 
 // data-gradient GEMM of a pointwise conv whose INPUT is the output of a conv+BN+act unit: dx = dy * W (W^T given, [K][Nc] rows = [Nc][K]
 // transposed -> NT), and in the same epilogue that unit's BN-backward reduction over (dx, its raw output y): the separate
 // mny_bn_bwd_reduce pass (one more read of dx and of y) disappears — only y is read, by the tile that just produced dx.
-// the reduction epilogue holds four more per-column constants and a group of loads: the 160-column tile (TN = 5) spills with it
-constexpr int kRedMaxTn = 4;
-static bool dgrad_bnred_ok(int64_t M, int K, int Nc, int act) {
-    if (K >= 512 && Nc >= 512) return false;      // matrix-pipe-bound: the reduce pass it would save is cheaper than the longer epilogue
-    if ((pw_thin_ok(0, 1, M, K, Nc) || pw_thin_ok(1, 1, M, K, Nc)) && act == MNY_ACT_HSIGMOID) return false;
-    if (pw_wide_ok(M, K, Nc, true) && act >= MNY_ACT_HSWISH) return false;      // the wide-output kernel's reduction form knows the clamp family (its h-swish builds spill)      // the short-reduction kernel knows the clamp family and h-swish (what units use)
-    return M > 0 && K > 0 && Nc > 0 && (K & 3) == 0 && act >= MNY_ACT_NONE && act <= MNY_ACT_HSIGMOID && !sw(SW_GEMM_V1);
-}
-extern "C" int mny_pw_dgrad_bnred_supported(int64_t M, int K, int Nc, int act) { return dgrad_bnred_ok(M, K, Nc, act) ? 1 : 0; }
-extern "C" int mny_pw_dgrad_bnred_parts(int64_t M, int K, int Nc) {
-    if (M <= 0 || K <= 0 || Nc <= 0 || (K & 3)) return MNY_EINVAL;
-    if (pw_thin_ok(0, 1, M, K, Nc)) return pw_thin_parts(M, K, Nc, 1);
-    if (pw_wide_ok(M, K, Nc, true)) return pw_wide_parts(M, K, Nc, true) + ((M & 31) ? nt2_plan(M & 31, K, Nc, false, 0, kRedMaxTn).gx : 0);
-    return nt2_plan(M, K, Nc, false, 0, kRedMaxTn).gx;
-}
 template <int BF>
 static int pw_dgrad_bnred_impl(const void* dy, const void* wT, void* dx, const void* y, const float* scale, const float* shift, int act,
-                               const float* mean, const float* invstd, float* red, int64_t M, int K, int Nc, void* stream, const void* addend = nullptr) {
+                               const float* mean, const float* invstd, float* red, int64_t M, int K, int Nc, void* stream, const void* addend = nullptr,
+                               bool planes = false) {
     MNY_REQUIRE(dy && wT && dx && y && scale && shift && mean && invstd && red, "pw_dgrad_bnred: null pointer");
-    MNY_REQUIRE(dgrad_bnred_ok(M, K, Nc, act) && (!BF || (K & 7) == 0), "pw_dgrad_bnred: unsupported problem M=%lld K=%d N=%d act=%d (see mny_pw_dgrad_bnred_supported)",
-                (long long)M, K, Nc, act);
-    if (BF && pwt_ok(M, K, Nc, MNY_ACT_NONE, false)) {       // K <= 48 at a large pixel count: a wave per 16 pixels (gate.hip)
-        g_pw_route = MNY_ROUTE_WAVE16;
-        return pwt_launch(dy, nullptr, nullptr, MNY_ACT_NONE, wT, addend, dx, red, M, K, Nc, (hipStream_t)stream, y, scale, shift, mean, invstd, act);
+    const PwRoute r = pw_dgrad_bnred_route(BF, M, K, Nc, act, addend != nullptr, planes);
+    MNY_REQUIRE(!r.why, "pw_dgrad_bnred: unsupported problem M=%lld K=%d N=%d act=%d: %s (see mny_pw_dgrad_bnred_supported)", (long long)M, K, Nc, act, r.why);
+    g_pw_route = r.family;
+    hipStream_t st = (hipStream_t)stream;
+    switch (r.family) {
+        case MNY_ROUTE_WAVE16: return pwt_launch(dy, nullptr, nullptr, MNY_ACT_NONE, wT, addend, dx, red, M, K, Nc, st, y, scale, shift, mean, invstd, act);
+        case MNY_ROUTE_THIN:
+            return pw_thin_launch(BF, dy, nullptr, nullptr, MNY_ACT_NONE, wT, nullptr, addend, dx, red, M, K, Nc, addend ? 2 : 1, y, scale, shift, mean, invstd, act, st);
+        case MNY_ROUTE_WIDE: {      // fp32: whole 32-row tiles; the last M % 32 rows follow below
+            const int rc = pw_wide_launch((const float*)dy, nullptr, nullptr, MNY_ACT_NONE, (const float*)wT, (float*)dx, red, r.Mf, K, Nc, (const float*)y, scale, shift,
+                                          mean, invstd, act, (const float*)addend, st);
+            if (rc != 0 || r.Mf == M) return rc;
+            red += (int64_t)r.wide_parts * 2 * Nc;
+            dy = (const float*)dy + r.Mf * K; dx = (float*)dx + r.Mf * Nc; y = (const float*)y + r.Mf * Nc;
+            if (addend) addend = (const float*)addend + r.Mf * Nc;
+            M -= r.Mf;
+        }
     }
-    if (pw_thin_ok(BF, 1, M, K, Nc)) g_pw_route = MNY_ROUTE_THIN;
-    if (pw_thin_ok(BF, 1, M, K, Nc))
-        return pw_thin_launch(BF, dy, nullptr, nullptr, MNY_ACT_NONE, wT, nullptr, addend, dx, red, M, K, Nc, addend ? 2 : 1, y, scale, shift, mean, invstd, act,
-                              (hipStream_t)stream);
-    bool took_wide = false;
-    if (!BF && pw_wide_ok(M, K, Nc, true)) {        // whole 32-row tiles on the barrier-free kernel, the last M % 32 rows below (one more partial row)
-        g_pw_route = MNY_ROUTE_WIDE;
-        took_wide = true;
-        const int64_t Mf = M & ~(int64_t)31;
-        const int rc = pw_wide_launch((const float*)dy, nullptr, nullptr, MNY_ACT_NONE, (const float*)wT, (float*)dx, red, Mf, K, Nc, (const float*)y, scale, shift,
-                                      mean, invstd, act, (const float*)addend, (hipStream_t)stream);
-        if (rc != 0 || Mf == M) return rc;
-        red += (int64_t)pw_wide_parts(M, K, Nc, true) * 2 * Nc;
-        dy = (const float*)dy + Mf * K; dx = (float*)dx + Mf * Nc; y = (const float*)y + Mf * Nc;
-        if (addend) addend = (const float*)addend + Mf * Nc;
-        M -= Mf;
-    }
-    Nt2Plan p2 = nt2_plan(M, K, Nc, false, BF, kRedMaxTn);
-    MNY_REQUIRE(p2.lds <= 64 * 1024, "pw_dgrad_bnred: K=%d too large", K);
-    Gemm2Args g{dy, nullptr, nullptr, MNY_ACT_NONE, wT, nullptr, addend, dx, red, M, K, Nc, p2.m_tiles, p2.tiles_per_block, p2.gx, p2.n_tiles,
+    Gemm2Args g{dy, nullptr, nullptr, MNY_ACT_NONE, wT, nullptr, addend, dx, red, M, K, Nc, r.p2.m_tiles, r.p2.tiles_per_block, r.p2.gx, r.p2.n_tiles,
                 y, scale, shift, mean, invstd, act};
-    Nt2Kernel k;
-    constexpr int X = BF ? 0 : 1;                   // the six-product bf16 form exists for fp32 operands only
-    const bool x6 = !BF && nt_x6(M, K, Nc);
-    if (!took_wide) g_pw_route = x6 ? MNY_ROUTE_DMA_X6 : MNY_ROUTE_DMA_F32;
-    if (addend) switch (p2.TN) {                    // RED = 2: with an addend (own instantiations: the addend loads cost the TN = 4 variant registers)
-        case 1: k = x6 ? (Nt2Kernel)pw_gemm_nt_dma_kernel<1, 0, BF, 2, X> : (Nt2Kernel)pw_gemm_nt_dma_kernel<1, 0, BF, 2>; break;
-        case 2: k = x6 ? (Nt2Kernel)pw_gemm_nt_dma_kernel<2, 0, BF, 2, X> : (Nt2Kernel)pw_gemm_nt_dma_kernel<2, 0, BF, 2>; break;
-        case 3: k = x6 ? (Nt2Kernel)pw_gemm_nt_dma_kernel<3, 0, BF, 2, X> : (Nt2Kernel)pw_gemm_nt_dma_kernel<3, 0, BF, 2>; break;
-        default: k = x6 ? (Nt2Kernel)pw_gemm_nt_dma_kernel<4, 0, BF, 2, X> : (Nt2Kernel)pw_gemm_nt_dma_kernel<4, 0, BF, 2>; break;
-    }
-    else switch (p2.TN) {
-        case 1: k = x6 ? (Nt2Kernel)pw_gemm_nt_dma_kernel<1, 0, BF, 1, X> : (Nt2Kernel)pw_gemm_nt_dma_kernel<1, 0, BF, 1>; break;
-        case 2: k = x6 ? (Nt2Kernel)pw_gemm_nt_dma_kernel<2, 0, BF, 1, X> : (Nt2Kernel)pw_gemm_nt_dma_kernel<2, 0, BF, 1>; break;
-        case 3: k = x6 ? (Nt2Kernel)pw_gemm_nt_dma_kernel<3, 0, BF, 1, X> : (Nt2Kernel)pw_gemm_nt_dma_kernel<3, 0, BF, 1>; break;
-        default: k = x6 ? (Nt2Kernel)pw_gemm_nt_dma_kernel<4, 0, BF, 1, X> : (Nt2Kernel)pw_gemm_nt_dma_kernel<4, 0, BF, 1>; break;
-    }
-    hipLaunchKernelGGL(k, dim3(p2.grid), dim3(256), p2.lds, (hipStream_t)stream, g);
-    return check_launch("pw_gemm_nt_dma_kernel<RED>");
+    return nt2_launch(r, 0, BF, addend ? 2 : 1, 0, g, st, "pw_gemm_nt_dma_kernel<RED>");
 }
+extern "C" int mny_pw_dgrad_bnred_supported(int64_t M, int K, int Nc, int act) { return !pw_dgrad_bnred_route(0, M, K, Nc, act, false, false).why; }
+extern "C" int mny_pw_dgrad_bnred_parts(int64_t M, int K, int Nc) { return pw_dgrad_bnred_route(0, M, K, Nc, MNY_ACT_NONE, false, false).parts; }
 extern "C" int mny_pw_dgrad_bnred(const float* dy, const float* wT, float* dx, const float* y, const float* scale, const float* shift, int act,
                                   const float* mean, const float* invstd, float* red, int64_t M, int K, int Nc, void* stream) {
     return pw_dgrad_bnred_impl<0>(dy, wT, dx, y, scale, shift, act, mean, invstd, red, M, K, Nc, stream);
 }
-// the addend variant exists for column tiles of <= 96 (TN <= 3: the 128-column tile has no registers left for the addend loads)
-extern "C" int mny_pw_dgrad_bnred_add_supported(int64_t M, int K, int Nc, int act) {
-    return dgrad_bnred_ok(M, K, Nc, act) && (pw_thin_ok(0, 1, M, K, Nc) || pw_wide_ok(M, K, Nc, true) || nt2_plan(M, K, Nc, false, 0, kRedMaxTn).TN <= 3) ? 1 : 0;
-}
-extern "C" int mny_pw_dgrad_bnred_add_supported_bf16(int64_t M, int K, int Nc, int act) {
-    return dgrad_bnred_ok(M, K, Nc, act) && (K & 7) == 0 && (pwt_ok(M, K, Nc, MNY_ACT_NONE, false) || pw_thin_ok(1, 1, M, K, Nc) || nt2_plan(M, K, Nc, false, 1, kRedMaxTn).TN <= 3) ? 1 : 0;
-}
+extern "C" int mny_pw_dgrad_bnred_add_supported(int64_t M, int K, int Nc, int act) { return !pw_dgrad_bnred_route(0, M, K, Nc, act, true, false).why; }
+extern "C" int mny_pw_dgrad_bnred_add_supported_bf16(int64_t M, int K, int Nc, int act) { return !pw_dgrad_bnred_route(1, M, K, Nc, act, true, false).why; }
 extern "C" int mny_pw_dgrad_bnred_add(const float* dy, const float* wT, const float* addend, float* dx, const float* y, const float* scale, const float* shift,
                                       int act, const float* mean, const float* invstd, float* red, int64_t M, int K, int Nc, void* stream) {
-    MNY_REQUIRE(addend && mny_pw_dgrad_bnred_add_supported(M, K, Nc, act), "pw_dgrad_bnred_add: null addend or unsupported shape (mny_pw_dgrad_bnred_add_supported)");
+    MNY_REQUIRE(addend, "pw_dgrad_bnred_add: null addend");
     return pw_dgrad_bnred_impl<0>(dy, wT, dx, y, scale, shift, act, mean, invstd, red, M, K, Nc, stream, addend);
 }
 extern "C" int mny_pw_dgrad_bnred_add_bf16(const void* dy, const void* wT, const void* addend, void* dx, const void* y, const float* scale, const float* shift,
                                            int act, const float* mean, const float* invstd, float* red, int64_t M, int K, int Nc, void* stream) {
-    MNY_REQUIRE(addend && mny_pw_dgrad_bnred_add_supported_bf16(M, K, Nc, act), "pw_dgrad_bnred_add: null addend or unsupported shape");
+    MNY_REQUIRE(addend, "pw_dgrad_bnred_add: null addend");
     return pw_dgrad_bnred_impl<1>(dy, wT, dx, y, scale, shift, act, mean, invstd, red, M, K, Nc, stream, addend);
 }
 // bf16 storage: dy, wT, dx, y are bf16; the sums are taken over the ROUNDED dx (what a separate reduce pass would read back)
-extern "C" int mny_pw_dgrad_bnred_supported_bf16(int64_t M, int K, int Nc, int act) { return dgrad_bnred_ok(M, K, Nc, act) && (K & 7) == 0 ? 1 : 0; }
-extern "C" int mny_pw_dgrad_bnred_parts_bf16(int64_t M, int K, int Nc) {
-    if (M <= 0 || K <= 0 || Nc <= 0 || (K & 7)) return MNY_EINVAL;
-    if (pwt_ok(M, K, Nc, MNY_ACT_NONE, false)) return pwt_parts(M);
-    if (pw_thin_ok(1, 1, M, K, Nc)) return pw_thin_parts(M, K, Nc, 1);
-    return nt2_plan(M, K, Nc, false, 1, kRedMaxTn).gx;
-}
+extern "C" int mny_pw_dgrad_bnred_supported_bf16(int64_t M, int K, int Nc, int act) { return !pw_dgrad_bnred_route(1, M, K, Nc, act, false, false).why; }
+extern "C" int mny_pw_dgrad_bnred_parts_bf16(int64_t M, int K, int Nc) { return pw_dgrad_bnred_route(1, M, K, Nc, MNY_ACT_NONE, false, false).parts; }
 extern "C" int mny_pw_dgrad_bnred_bf16(const void* dy, const void* wT, void* dx, const void* y, const float* scale, const float* shift, int act,
                                        const float* mean, const float* invstd, float* red, int64_t M, int K, int Nc, void* stream) {
     return pw_dgrad_bnred_impl<1>(dy, wT, dx, y, scale, shift, act, mean, invstd, red, M, K, Nc, stream);
@@ -2863,60 +2988,26 @@ extern "C" int mny_pw_dgrad_bnred_bf16(const void* dy, const void* wT, void* dx,
 // ---- low-rank BatchNorm-backward correction of a wide expand unit's data gradient (csrc/lrbwd.hip) ----------------------------------
 // dx = view(x) Q + r + addend  (x the K-wide input of the unit behind its LINEAR view in_scale / in_shift — applied where the A fragment is read,
 // as in every forward GEMM —, Q [K][K] symmetric and r [K] from mny_lr_prep, addend = the main term dzc W, usually dx itself); with `red` the
-// BN-backward sums of the unit whose complete output gradient dx now is (its raw output ry, as mny_pw_dgrad_bnred_add).  Always the LDS-DMA
-// kernel, column tiles of <= 96 (the addend form's limit).
-static bool lr_fix_wide(int64_t M, int K, int r_act) {       // which kernel a call WITH a reduction target takes — the one rule for the launch and the row count
-    return pw_wide_fix_ok(M, K) && r_act < MNY_ACT_HSWISH;
-}
-static int pw_lr_fix_impl(const float* x, const float* in_scale, const float* in_shift, const float* q, const float* r, const float* addend, float* dx,
-                          const float* ry, const float* r_scale, const float* r_shift, int r_act, const float* r_mean, const float* r_invstd, float* red,
-                          int64_t M, int K, void* stream) {
-    MNY_REQUIRE(x && q && r && addend && dx && M > 0 && K > 0 && (K & 3) == 0 && (!in_scale) == (!in_shift), "pw_lr_fix: bad arguments (K=%d)", K);
-    MNY_REQUIRE(!red || (ry && r_scale && r_shift && r_mean && r_invstd && r_act >= MNY_ACT_NONE && r_act <= MNY_ACT_HSIGMOID), "pw_lr_fix: incomplete reduction target");
-    const bool xf = in_scale != nullptr;
-    if (red && lr_fix_wide(M, K, r_act)) {            // K = 64 / 96 at whole 32-row tiles: the barrier-free kernel of pwwide.hip
-        g_pw_route = MNY_ROUTE_WIDE;
-        return pw_wide_fix_launch(x, in_scale, in_shift, q, r, addend, dx, red, M, K, ry, r_scale, r_shift, r_mean, r_invstd, r_act, (hipStream_t)stream);
-    }
-    Nt2Plan p2 = nt2_plan(M, K, K, xf, 0, 3);
-    MNY_REQUIRE(p2.lds <= 64 * 1024, "pw_lr_fix: K=%d too large", K);
-    Gemm2Args g{x, in_scale, in_shift, MNY_ACT_NONE, q, r, addend, dx, red, M, K, K, p2.m_tiles, p2.tiles_per_block, p2.gx, p2.n_tiles,
-                ry, r_scale, r_shift, r_mean, r_invstd, r_act};
-    const bool x6 = nt_x6(M, K, K);
-    Nt2Kernel k;
-#define MNY_FX(T) (xf ? (x6 ? (Nt2Kernel)pw_gemm_nt_dma_kernel<T, 1, 0, 2, 1, 1> : (Nt2Kernel)pw_gemm_nt_dma_kernel<T, 1, 0, 2, 0, 1>) \
-                      : (x6 ? (Nt2Kernel)pw_gemm_nt_dma_kernel<T, 0, 0, 2, 1, 1> : (Nt2Kernel)pw_gemm_nt_dma_kernel<T, 0, 0, 2, 0, 1>))
-    if (red) switch (p2.TN) { case 1: k = MNY_FX(1); break; case 2: k = MNY_FX(2); break; default: k = MNY_FX(3); break; }
-    else k = nt2_kernel(p2.TN, xf ? 1 : 0, 0, x6 ? 1 : 0);
-#undef MNY_FX
-    g_pw_route = x6 ? MNY_ROUTE_DMA_X6 : MNY_ROUTE_DMA_F32;
-    hipLaunchKernelGGL(k, dim3(p2.grid), dim3(256), p2.lds, (hipStream_t)stream, g);
-    return check_launch("pw_gemm_nt_dma_kernel<lr_fix>");
-}
-extern "C" int mny_pw_lr_fix_parts(int64_t M, int K, int r_act) {
-    if (M <= 0 || K <= 0 || (K & 3)) return MNY_EINVAL;
-    return lr_fix_wide(M, K, r_act) ? pw_wide_fix_parts(M, K) : nt2_plan(M, K, K, true, 0, 3).gx;
-}
+// BN-backward sums of the unit whose complete output gradient dx now is (its raw output ry, as mny_pw_dgrad_bnred_add).
+extern "C" int mny_pw_lr_fix_parts(int64_t M, int K, int r_act) { return pw_lr_fix_route(M, K, r_act, true, false).parts; }
 extern "C" int mny_pw_lr_fix(const float* x, const float* in_scale, const float* in_shift, const float* q, const float* r, const float* addend, float* dx,
                              const float* ry, const float* r_scale, const float* r_shift, int r_act, const float* r_mean, const float* r_invstd, float* red,
                              int64_t M, int K, void* stream) {
-    return pw_lr_fix_impl(x, in_scale, in_shift, q, r, addend, dx, ry, r_scale, r_shift, r_act, r_mean, r_invstd, red, M, K, stream);
+    MNY_REQUIRE(x && q && r && addend && dx && (!in_scale) == (!in_shift), "pw_lr_fix: bad arguments (K=%d)", K);
+    MNY_REQUIRE(!red || (ry && r_scale && r_shift && r_mean && r_invstd && r_act >= MNY_ACT_NONE && r_act <= MNY_ACT_HSIGMOID), "pw_lr_fix: incomplete reduction target");
+    const bool xf = in_scale != nullptr;
+    const PwRoute rt = pw_lr_fix_route(M, K, r_act, red != nullptr, xf);
+    MNY_REQUIRE(!rt.why, "pw_lr_fix: bad arguments (M=%lld K=%d): %s", (long long)M, K, rt.why);
+    g_pw_route = rt.family;
+    if (rt.family == MNY_ROUTE_WIDE)
+        return pw_wide_fix_launch(x, in_scale, in_shift, q, r, addend, dx, red, M, K, ry, r_scale, r_shift, r_mean, r_invstd, r_act, (hipStream_t)stream);
+    Gemm2Args g{x, in_scale, in_shift, MNY_ACT_NONE, q, r, addend, dx, red, M, K, K, rt.p2.m_tiles, rt.p2.tiles_per_block, rt.p2.gx, rt.p2.n_tiles,
+                ry, r_scale, r_shift, r_mean, r_invstd, r_act};
+    return nt2_launch(rt, xf ? 1 : 0, 0, red ? 2 : 0, red ? 1 : 0, g, (hipStream_t)stream, "pw_gemm_nt_dma_kernel<lr_fix>");
 }
 
-// ---- forward / data-gradient GEMMs on pre-cut weight planes (fp32 plans, six-product form) ---------------------------------------
-// Planes pay where the matrix pipe is the bound.  Round 2: a stage of B grew from 64 to 96 bytes per row, which cost the mid-size shapes
-// their third resident workgroup (7-18 % faster from ~60 FLOP per byte up, 10-30 % slower below ~40).  Round 3: the plane ring is two
-// slots deep (the A ring stays at three), the LDS footprint equals the plain mode's and the threshold moved down to 30 FLOP per byte.
-static bool w6_ok(int64_t M, int K, int Nc) {
-    const bool off = sw(SW_NO_W6);
-    // (round 3: with the two-slot plane ring the planes no longer cost a resident workgroup; same-box A/B per shape: K576 N96 -11 %,
-    // K384 N96 -10 %, the 75-channel heads -9..-11 %, K384 N64 (27 FLOP per byte) +0..+7 % -> threshold 30, was 50)
-    constexpr double min_ai = 30.0;
-    const double ai = 2.0 * K * Nc / (4.0 * (K + Nc));
-    return !off && M > 0 && K > 0 && Nc > 0 && (K & 3) == 0 && !pw_thin_ok(0, 0, M, K, Nc) && !pw_wide_ok(M, K, Nc, false) && !pw_wide_ok(M, K, Nc, true) && nt_x6(M, K, Nc) != 0 && ai >= min_ai &&
-           !sw(SW_GEMM_V1);
-}
-extern "C" int mny_pw_w6_supported(int64_t M, int K, int Nc) { return w6_ok(M, K, Nc) ? 1 : 0; }
+// ---- forward / data-gradient GEMMs on pre-cut weight planes (fp32 plans, six-product form; w6_pays above) -------------------------------
+extern "C" int mny_pw_w6_supported(int64_t M, int K, int Nc) { return !pw_fwd_route(0, M, K, Nc, MNY_ACT_NONE, false, false, false, true).why; }
 extern "C" size_t mny_pw_w6_bytes(int K, int Nc) { return (K <= 0 || Nc <= 0) ? 0 : (size_t)3 * Nc * ((K + 15) / 16) * 32; }
 extern "C" int mny_cut3_batch(const mny_cut3_job* jobs, const int32_t* block_job, int nblocks, void* stream) {
     MNY_REQUIRE(jobs && block_job && nblocks > 0, "cut3_batch: bad arguments");
@@ -2925,180 +3016,84 @@ extern "C" int mny_cut3_batch(const mny_cut3_job* jobs, const int32_t* block_job
     return check_launch("cut3_batch_kernel");
 }
 extern "C" int mny_pw_fwd_w6(const float* x, const float* in_scale, const float* in_shift, int in_act, const void* w6, const float* bias,
-                             const float* addend, float* y, float* stats, int64_t M, int K, int Nc, void* stream) {
-    MNY_REQUIRE(x && w6 && y, "pw_fwd_w6: null pointer");
-    MNY_REQUIRE(w6_ok(M, K, Nc), "pw_fwd_w6: unsupported problem M=%lld K=%d N=%d (mny_pw_w6_supported)", (long long)M, K, Nc);
-    MNY_REQUIRE(!(stats && bias), "pw_fwd_w6: stats and bias are mutually exclusive");
-    const bool xf = in_scale != nullptr || in_act != MNY_ACT_NONE;
-    Nt2Plan p2 = nt2_plan(M, K, Nc, xf);                          // same tiling and partial rows as mny_pw_fwd
-#if MNY_W6_SWP
-    // software-pipelined form: three-slot A ring + THREE-slot plane ring (24 + 9 TN KB) + the scale / shift cache
-    const int Kpad16 = (int)cdiv(K, 16) * 16;
-    const size_t lds = (size_t)(3 * BM * 16 + 3 * 32 * p2.TN * 24) * sizeof(float) + (xf ? 2 * Kpad16 * sizeof(float) : 0);
-#else
-    const size_t lds = p2.lds;                                    // three-slot A ring + two-slot plane ring = the plain mode's three-slot (A + fp32 B) ring, to the byte
-#endif
-    MNY_REQUIRE(lds <= 96 * 1024, "pw_fwd_w6: K=%d too large for the LDS scale cache", K);
-    Gemm2Args g{x, in_scale, in_shift, in_act, w6, bias, addend, y, stats, M, K, Nc, p2.m_tiles, p2.tiles_per_block, p2.gx, p2.n_tiles,
-                nullptr, nullptr, nullptr, nullptr, nullptr, 0};
-    const int XF = !xf ? 0 : (in_act == MNY_ACT_HSWISH ? 2 : 1);
-    const Nt2Kernel k = nt2_kernel(p2.TN, XF, 0, 3);
-    g_pw_route = MNY_ROUTE_DMA_X6;
-    nt2_allow_lds(k, lds);
-    hipLaunchKernelGGL(k, dim3(p2.grid), dim3(256), lds, (hipStream_t)stream, g);
-    return check_launch("pw_gemm_nt_dma_kernel<w6>");
+                             const float* addend, float* y, float* stats, int64_t M, int K, int Nc, void* stream) {      // same tiling and partial rows as mny_pw_fwd
+    return pw_fwd_impl<0>(x, in_scale, in_shift, in_act, w6, bias, addend, y, stats, M, K, Nc, stream, true);
 }
 // data gradient + BN-backward sums of the fed unit (mny_pw_dgrad_bnred / _add semantics; addend may be NULL) on pre-cut W^T planes
 extern "C" int mny_pw_dgrad_bnred_w6(const float* dy, const void* wT6, const float* addend, float* dx, const float* y, const float* scale,
                                      const float* shift, int act, const float* mean, const float* invstd, float* red, int64_t M, int K, int Nc,
                                      void* stream) {
-    MNY_REQUIRE(dy && wT6 && dx && y && scale && shift && mean && invstd && red, "pw_dgrad_bnred_w6: null pointer");
-    MNY_REQUIRE(w6_ok(M, K, Nc) && dgrad_bnred_ok(M, K, Nc, act), "pw_dgrad_bnred_w6: unsupported problem M=%lld K=%d N=%d", (long long)M, K, Nc);
-    Nt2Plan p2 = nt2_plan(M, K, Nc, false, 0, kRedMaxTn);
-    MNY_REQUIRE(!addend || p2.TN <= 3, "pw_dgrad_bnred_w6: the addend form needs a column tile of <= 96 (mny_pw_dgrad_bnred_add_supported)");
-    const size_t lds = p2.lds;
-    MNY_REQUIRE(lds <= 96 * 1024, "pw_dgrad_bnred_w6: K=%d too large", K);
-    Gemm2Args g{dy, nullptr, nullptr, MNY_ACT_NONE, wT6, nullptr, addend, dx, red, M, K, Nc, p2.m_tiles, p2.tiles_per_block, p2.gx, p2.n_tiles,
-                y, scale, shift, mean, invstd, act};
-    Nt2Kernel k;
-    if (addend) switch (p2.TN) {
-        case 1: k = (Nt2Kernel)pw_gemm_nt_dma_kernel<1, 0, 0, 2, 3>; break; case 2: k = (Nt2Kernel)pw_gemm_nt_dma_kernel<2, 0, 0, 2, 3>; break;
-        default: k = (Nt2Kernel)pw_gemm_nt_dma_kernel<3, 0, 0, 2, 3>; break;
-    }
-    else switch (p2.TN) {
-        case 1: k = (Nt2Kernel)pw_gemm_nt_dma_kernel<1, 0, 0, 1, 3>; break; case 2: k = (Nt2Kernel)pw_gemm_nt_dma_kernel<2, 0, 0, 1, 3>; break;
-        case 3: k = (Nt2Kernel)pw_gemm_nt_dma_kernel<3, 0, 0, 1, 3>; break; default: k = (Nt2Kernel)pw_gemm_nt_dma_kernel<4, 0, 0, 1, 3>; break;
-    }
-    g_pw_route = MNY_ROUTE_DMA_X6;
-    nt2_allow_lds(k, lds);
-    hipLaunchKernelGGL(k, dim3(p2.grid), dim3(256), lds, (hipStream_t)stream, g);
-    return check_launch("pw_gemm_nt_dma_kernel<RED, w6>");
+    return pw_dgrad_bnred_impl<0>(dy, wT6, dx, y, scale, shift, act, mean, invstd, red, M, K, Nc, stream, addend, true);
 }
 
-extern "C" int mny_pw_fwd_bf16(const void* x, const float* in_scale, const float* in_shift, int in_act, const void* w,
-                               const float* bias, const void* addend, void* y, float* stats, int64_t M, int K, int Nc,
-                               void* stream) {
-    MNY_REQUIRE(x && w && y, "pw_fwd: null pointer");
-    MNY_REQUIRE(M > 0 && K > 0 && Nc > 0, "pw_fwd: empty problem");
-    MNY_REQUIRE(!(stats && bias), "pw_fwd: stats and bias are mutually exclusive");
-    hipStream_t st = (hipStream_t)stream;
-    const bool xf = in_scale != nullptr || in_act != MNY_ACT_NONE;
-    const bool force_v1 = sw(SW_GEMM_V1);
-    // mny_pw_stat_parts_bf16 sizes the caller's partial rows from (M, K, Nc) alone: a view / bias that moves the call to another kernel family
-    // than the query assumed would write a different number of rows than mny_bn_finalize sums — refuse it instead
-    MNY_REQUIRE(!stats || pwt_ok(M, K, Nc, in_act, bias != nullptr) == pwt_ok(M, K, Nc, MNY_ACT_NONE, false),
-                "pw_fwd_bf16: statistics with in_act=%d at M=%lld K=%d N=%d take another kernel family than mny_pw_stat_parts_bf16 counted rows for", in_act, (long long)M, K, Nc);
-    if (pwt_ok(M, K, Nc, in_act, bias != nullptr))         // K <= 48 at a large pixel count: a wave per 16 pixels on the bf16 matrix cores (gate.hip)
-        return (g_pw_route = MNY_ROUTE_WAVE16, pwt_launch(x, in_scale, in_shift, in_act, w, addend, y, stats, M, K, Nc, st));
-    if (pw_thin_ok(1, 0, M, K, Nc))
-        return (g_pw_route = MNY_ROUTE_THIN, pw_thin_launch(1, x, in_scale, in_shift, in_act, w, bias, addend, y, stats, M, K, Nc, 0, nullptr, nullptr, nullptr, nullptr, nullptr, 0, st));
-    if ((K & 7) == 0 && !force_v1) {                // LDS-DMA pipeline on the bf16 matrix cores (16-B aligned bf16 rows)
-        Nt2Plan p2 = nt2_plan(M, K, Nc, xf, 1);
-        MNY_REQUIRE(p2.lds <= 64 * 1024, "pw_fwd: K=%d too large for the LDS scale cache", K);
-        Gemm2Args g{x, in_scale, in_shift, in_act, w, bias, addend, y, stats, M, K, Nc, p2.m_tiles, p2.tiles_per_block, p2.gx, p2.n_tiles,
-                    nullptr, nullptr, nullptr, nullptr, nullptr, 0};
-        const int XF = !xf ? 0 : (in_act == MNY_ACT_HSWISH ? 2 : 1);
-        g_pw_route = MNY_ROUTE_DMA_F32;
-        hipLaunchKernelGGL(nt2_kernel(p2.TN, XF, 1), dim3(p2.grid), dim3(256), p2.lds, st, g);
-        return check_launch("pw_gemm_nt_dma_kernel<bf16>");
-    }
-    g_pw_route = MNY_ROUTE_TILE_V1;
-    return pw_fwd_v1<bf16_t>((const bf16_t*)x, in_scale, in_shift, in_act, (const bf16_t*)w, bias, (const bf16_t*)addend, (bf16_t*)y, stats,
-                             M, K, Nc, st);
-}
-
-// which kernel family the LAST pointwise-conv call of this thread took — set by the dispatchers themselves where they decide, so it cannot
-// drift from them (the predictor below ignores h-swish views / bias gradients).  engine.py records it for every call of a plan's
-// first replay; NetPlan.kernel_routes() reports those.
+// which kernel family the LAST pointwise-conv call of this thread took — every launcher assigns it once, from its route.  engine.py records it
+// for every call of a plan's first replay; NetPlan.kernel_routes() reports those.
 extern "C" int mny_pw_last_route(void) { return g_pw_route; }
 
-// PREDICTED kernel family of a call with a plain view (no h-swish input, no bias gradient): the predicates of the three dispatchers in
-// their order.  For shapes no plan at hand launches (tests ask it about the bs-256 shapes while running a bs-64 plan).
+// The kernel family of a call with a plain view (no input view, bias, addend or bias gradient): the launchers' own route functions evaluated for
+// that call, so for a plain call it is what mny_pw_last_route reports afterwards.  A call behind an h-swish view or with a bias (gradient) can
+// take another family.  For shapes no plan at hand launches (tests ask it about the bs-256 shapes while running a bs-64 plan).
 extern "C" int mny_pw_route(int op, int bf16, int64_t M, int K, int Nc) {
     if (M <= 0 || K <= 0 || Nc <= 0 || op < 0 || op > 2) return MNY_EINVAL;
-    const bool gemm_v1 = sw(SW_GEMM_V1), wgrad_v1 = sw(SW_WGRAD_V1);
-    const int al = bf16 ? 7 : 3;
-    if (op == 2) {
-        if (!bf16 && pw_wgs_ok(M, K, Nc)) return MNY_ROUTE_WGRAD_STREAM;
-        if ((Nc & al) || (K & al) || wgrad_v1) return MNY_ROUTE_TILE_V1;
-        return (!bf16 && nt_x6(M, K, Nc)) ? MNY_ROUTE_DMA_X6 : MNY_ROUTE_DMA_F32;
-    }
-    if (bf16 && op == 0 && pwt_ok(M, K, Nc, MNY_ACT_NONE, false)) return MNY_ROUTE_WAVE16;
-    if (pw_thin_ok(bf16 ? 1 : 0, op, M, K, Nc)) return MNY_ROUTE_THIN;
-    if (!bf16 && pw_wide_ok(M, K, Nc, op == 1)) return MNY_ROUTE_WIDE;
-    if ((K & al) || gemm_v1) return MNY_ROUTE_TILE_V1;
-    return (!bf16 && nt_x6(M, K, Nc)) ? MNY_ROUTE_DMA_X6 : MNY_ROUTE_DMA_F32;
+    const int bf = bf16 ? 1 : 0;
+    if (op == 0) return pw_fwd_route(bf, M, K, Nc, MNY_ACT_NONE, false, false, false, false).family;
+    if (op == 1) return pw_dgrad_bnred_route(bf, M, K, Nc, MNY_ACT_NONE, false, false).family;
+    return pw_wgrad_route(bf, M, K, Nc, MNY_ACT_NONE, false).family;
 }
 
+// room for whichever kernel the call takes: with a bias gradient the narrow-sided shapes stay off the stream kernel
 extern "C" size_t mny_pw_wgrad_ws_floats(int64_t M, int K, int Nc) {
     if (M <= 0 || K <= 0 || Nc <= 0) return 0;
-    WgPlan pl = wg_plan(M, K, Nc);
-    size_t splits = (size_t)pl.splits;
-    if (pw_wgs_ok(M, K, Nc) && (size_t)pw_wgs_splits(M, K, Nc) > splits) splits = (size_t)pw_wgs_splits(M, K, Nc);     // whichever kernel the call takes
-    return splits * Nc * K + (size_t)colsum_parts(M) * Nc;
+    const int a = pw_wgrad_route(0, M, K, Nc, MNY_ACT_NONE, false).parts, b = pw_wgrad_route(0, M, K, Nc, MNY_ACT_NONE, true).parts;
+    return (size_t)(a > b ? a : b) * Nc * K + (size_t)colsum_parts(M) * Nc;
 }
-
-// (without a bias gradient the narrow-sided shapes run the stream kernel of pwwgs.hip: its partial-row count)
-extern "C" int mny_pw_wgrad_splits(int64_t M, int K, int Nc) {
-    if (M <= 0 || K <= 0 || Nc <= 0) return MNY_EINVAL;
-    return pw_wgs_ok(M, K, Nc) ? pw_wgs_splits(M, K, Nc) : wg_plan(M, K, Nc, false).splits;
-}
-extern "C" int mny_pw_wgrad_splits_bf16(int64_t M, int K, int Nc) { return (M <= 0 || K <= 0 || Nc <= 0) ? MNY_EINVAL : wg_plan(M, K, Nc, true).splits; }
+extern "C" int mny_pw_wgrad_splits(int64_t M, int K, int Nc) { return pw_wgrad_route(0, M, K, Nc, MNY_ACT_NONE, false).parts; }
+extern "C" int mny_pw_wgrad_splits_bf16(int64_t M, int K, int Nc) { return pw_wgrad_route(1, M, K, Nc, MNY_ACT_NONE, false).parts; }
 
 template <typename T>
 static int pw_wgrad_impl(const T* x, const float* in_scale, const float* in_shift, int in_act, const T* dy,
                          float* dw, float* dbias, float* ws, int64_t M, int K, int Nc, void* stream) {
     MNY_REQUIRE(x && dy && ws, "pw_wgrad: null pointer");
     MNY_REQUIRE(dw || !dbias, "pw_wgrad: a deferred combine (dw == NULL) cannot carry a bias gradient");
-    MNY_REQUIRE(M > 0 && K > 0 && Nc > 0, "pw_wgrad: empty problem");
     constexpr bool is_f32 = sizeof(T) == 4;
-    if (is_f32 && pw_wgs_ok(M, K, Nc) && !dbias) {              // narrow-sided shape: barrier-free stream kernel (pwwgs.hip), partial rows [pw_wgs_splits][Nc][K]
-        g_pw_route = MNY_ROUTE_WGRAD_STREAM;
-        int rc = pw_wgs_launch((const float*)x, in_scale, in_shift, in_act, (const float*)dy, ws, M, K, Nc, (hipStream_t)stream);
+    const PwRoute r = pw_wgrad_route(!is_f32, M, K, Nc, in_act, dbias != nullptr);
+    MNY_REQUIRE(!r.why, "pw_wgrad: %s", r.why);
+    g_pw_route = r.family;
+    hipStream_t st = (hipStream_t)stream;
+    if (r.family == MNY_ROUTE_WGRAD_STREAM) {              // partial rows [r.parts][Nc][K]
+        int rc = pw_wgs_launch((const float*)x, in_scale, in_shift, in_act, (const float*)dy, ws, M, K, Nc, st);
         if (rc || !dw) return rc;
         const int64_t n = (int64_t)Nc * K;
-        hipLaunchKernelGGL(reduce_parts_kernel, dim3((unsigned)cdiv(n, 32)), dim3(256), 0, (hipStream_t)stream, ws, pw_wgs_splits(M, K, Nc), n, dw);
+        hipLaunchKernelGGL(reduce_parts_kernel, dim3((unsigned)cdiv(n, 32)), dim3(256), 0, st, ws, r.parts, n, dw);
         return check_launch("reduce_parts_kernel");
     }
-    const bool force_v1 = sw(SW_WGRAD_V1);
-    const bool dma_f32 = is_f32 && (Nc & 3) == 0 && (K & 3) == 0 && in_act != MNY_ACT_HSWISH && !force_v1;
-    WgPlan pl = wg_plan(M, K, Nc, !is_f32, dma_f32);
+    const WgPlan& pl = r.wg;
     WgradArgs a{x, in_scale, in_shift, in_act, dy, ws, M, K, Nc, pl.rows_per_block, 0, pl.gy, pl.splits};
     dim3 grid(pl.gx, pl.gy, pl.splits), block(256);
-    const bool xcd_order = !sw(SW_WGRAD_NO_XCD);      // (same-box A/B switch)
-    WgradArgs a_dma = a;
-    // (only with >= 64 splits, i.e. >= 8 per XCD: K1280 N512 — 40 tiles, 38 splits — lost 11 % to XCD imbalance)
-    const bool use_xcd = xcd_order && pl.gx * pl.gy > 1 && pl.splits >= 64;
-    if (use_xcd) a_dma.gx = pl.gx;
-    const dim3 grid_dma = use_xcd ? dim3((unsigned)(cdiv(pl.splits, 8) * 8 * pl.gx * pl.gy)) : grid;
-    hipStream_t st = (hipStream_t)stream;
-    WgKernel dk = nullptr;                       // LDS-DMA kernels read raw 16-B chunks: aligned rows only
-    if (is_f32) {
-        if (dma_f32) dk = wg_dma_kernel(pl.mode, pl.TI, pl.TJ, nt_x6(M, K, Nc));
-        if (dk && pl.lds_dma > 64 * 1024 && !allow_lds((const void*)dk, 160 * 1024)) { set_error("pw_wgrad: hipFuncSetAttribute failed"); return MNY_EHIP; }
-    } else if ((Nc & 7) == 0 && (K & 7) == 0 && !force_v1) {
+    if (r.family != MNY_ROUTE_TILE_V1) {                   // LDS-DMA kernels
         const int XF = (in_scale == nullptr && in_act == MNY_ACT_NONE) ? 0 : (in_act == MNY_ACT_HSWISH ? 2 : 1);
-        dk = wg_bf16_kernel(pl.mode, pl.TI, pl.TJ, XF);
-        if (dk && pl.lds_dma > 64 * 1024) {      // > 64 KB of dynamic LDS needs a per-kernel opt-in (once)
-            if (!allow_lds((const void*)dk, 160 * 1024)) {
-                set_error("pw_wgrad: hipFuncSetAttribute failed"); return MNY_EHIP;
-            }
+        const WgKernel dk = is_f32 ? wg_dma_kernel(pl.mode, pl.TI, pl.TJ, r.x6) : wg_bf16_kernel(pl.mode, pl.TI, pl.TJ, XF);
+        if (!dk) {
+            set_error("pw_wgrad: no kernel for mode %d tile %dx%d", pl.mode, pl.TI, pl.TJ); return MNY_EUNSUPPORTED;
         }
-    }
-    const int key = dk ? -1 : pl.mode * 100 + pl.TI * 10 + pl.TJ;
-    g_pw_route = !dk ? MNY_ROUTE_TILE_V1 : ((is_f32 && nt_x6(M, K, Nc)) ? MNY_ROUTE_DMA_X6 : MNY_ROUTE_DMA_F32);
-    if (dk) hipLaunchKernelGGL(dk, grid_dma, block, pl.lds_dma, st, a_dma);
-#define MNY_WG(MD, I, J) hipLaunchKernelGGL((pw_wgrad_kernel<T, MD, I, J>), grid, block, pl.lds, st, a)
-    switch (key) {
-        case -1: break;
-        case 11: MNY_WG(0, 1, 1); break; case 12: MNY_WG(0, 1, 2); break; case 21: MNY_WG(0, 2, 1); break; case 22: MNY_WG(0, 2, 2); break;
-        case 111: MNY_WG(1, 1, 1); break; case 112: MNY_WG(1, 1, 2); break; case 113: MNY_WG(1, 1, 3); break; case 114: MNY_WG(1, 1, 4); break;
-        case 115: MNY_WG(1, 1, 5); break; case 116: MNY_WG(1, 1, 6); break; case 121: MNY_WG(1, 2, 1); break; case 122: MNY_WG(1, 2, 2); break;
-        case 123: MNY_WG(1, 2, 3); break; case 131: MNY_WG(1, 3, 1); break; case 132: MNY_WG(1, 3, 2); break; case 141: MNY_WG(1, 4, 1); break;
-        case 151: MNY_WG(1, 5, 1); break; case 161: MNY_WG(1, 6, 1); break;
-        default: set_error("pw_wgrad: no kernel for mode %d tile %dx%d", pl.mode, pl.TI, pl.TJ); return MNY_EUNSUPPORTED;
-    }
+        if (pl.lds_dma > 64 * 1024 && !allow_lds((const void*)dk, 160 * 1024)) {      // > 64 KB of dynamic LDS needs a per-kernel opt-in (once)
+            set_error("pw_wgrad: hipFuncSetAttribute failed"); return MNY_EHIP;
+        }
+        // workgroups grouped per XCD (MNY_WGRAD_NO_XCD: same-box A/B switch) — only with >= 64 splits, i.e. >= 8 per XCD: K1280 N512 — 40 tiles,
+        // 38 splits — lost 11 % to XCD imbalance
+        const bool use_xcd = !sw(SW_WGRAD_NO_XCD) && pl.gx * pl.gy > 1 && pl.splits >= 64;
+        if (use_xcd) a.gx = pl.gx;
+        hipLaunchKernelGGL(dk, use_xcd ? dim3((unsigned)(cdiv(pl.splits, 8) * 8 * pl.gx * pl.gy)) : grid, block, pl.lds_dma, st, a);
+    } else {
+#define MNY_WG(MD, I, J) case MD * 100 + I * 10 + J: hipLaunchKernelGGL((pw_wgrad_kernel<T, MD, I, J>), grid, block, pl.lds, st, a); break;
+        switch (pl.mode * 100 + pl.TI * 10 + pl.TJ) {
+            MNY_WG(0, 1, 1) MNY_WG(0, 1, 2) MNY_WG(0, 2, 1) MNY_WG(0, 2, 2)
+            MNY_WG(1, 1, 1) MNY_WG(1, 1, 2) MNY_WG(1, 1, 3) MNY_WG(1, 1, 4) MNY_WG(1, 1, 5) MNY_WG(1, 1, 6) MNY_WG(1, 2, 1) MNY_WG(1, 2, 2) MNY_WG(1, 2, 3)
+            MNY_WG(1, 3, 1) MNY_WG(1, 3, 2) MNY_WG(1, 4, 1) MNY_WG(1, 5, 1) MNY_WG(1, 6, 1)
+            default: set_error("pw_wgrad: no kernel for mode %d tile %dx%d", pl.mode, pl.TI, pl.TJ); return MNY_EUNSUPPORTED;
+        }
 #undef MNY_WG
+    }
     int rc = check_launch("pw_wgrad_kernel");
     if (rc) return rc;
     if (!dw) return MNY_OK;                         // partials only: the caller combines them (mny_reduce_batch)
@@ -3181,12 +3176,19 @@ extern "C" int mny_transpose_bf16(const float* src, void* dst, int R, int Cc, vo
 // ---- fused BN-backward + wgrad + dgrad for thin "expand" units ------------------------------------------------
 extern "C" int mny_pw_bnbwd_supported(int64_t M, int K, int Nc) { return bnw_supported(M, K, Nc) ? 1 : 0; }
 
+// the workspace of mny_pw_bnbwd[_bf16]: partials [splits] | reduced row | B1 | Q | bias | 1-bit activation mask (npairs * TI 64-bit words)
+struct BnwWs { size_t red, B1, Q, bias, mask; int64_t npairs; size_t floats; };      // offsets and the total, in floats
+static BnwWs bnw_ws(const BnwPlan& pl, int64_t M, int K, int Nc) {
+    const size_t stride = (size_t)bnw_stride(Nc, K);
+    const size_t red = (size_t)pl.splits * stride, B1 = red + stride, Q = B1 + (size_t)Nc * K, bias = Q + (size_t)K * K;
+    const size_t mask = (bias + 64 + 15) / 16 * 16;                    // 64-byte aligned mask words
+    const int64_t npairs = (M / 2 + 66) / 2 * 2;                       // even (16-B aligned rows of words) + a tile of slack
+    return {red, B1, Q, bias, mask, npairs, bias + 64 + 64 + (size_t)npairs * pl.TI * 2};
+}
 extern "C" size_t mny_pw_bnbwd_ws_floats(int64_t M, int K, int Nc) {
     if (!bnw_supported(M, K, Nc)) return 0;
-    BnwPlan pl = bnw_plan(M, K, Nc);
-    // partials + reduced row + B1 + Q + bias + 1-bit activation mask (M/2 * TI 64-bit words); the wave form of bf16 storage (gate.hip) lays its own
-    // buffers out in the same workspace: the larger of the two
-    const size_t base = (size_t)(pl.splits + 1) * bnw_stride(Nc, K) + (size_t)Nc * K + (size_t)K * K + 64 + 64 + (size_t)((M / 2 + 66) / 2 * 2) * pl.TI * 2;
+    // the wave form of bf16 storage (gate.hip) lays its own buffers out in the same workspace: the larger of the two
+    const size_t base = bnw_ws(bnw_plan(M, K, Nc), M, K, Nc).floats;
     const size_t wave = pwe_ok(M, K, Nc) ? pwe_ws_floats(M, K, Nc) : 0;
     return base > wave ? base : wave;
 }
@@ -3215,15 +3217,10 @@ static int pw_bnbwd_impl(const float* g, const float* y, const float* scale, con
     BnwPlan pl = bnw_plan(M, K, Nc);
     hipStream_t st = (hipStream_t)stream;
     const int64_t stride = bnw_stride(Nc, K);
-    float* red = ws + (size_t)pl.splits * stride;
-    float* B1 = red + stride;
-    float* Q = B1 + (size_t)Nc * K;
-    float* bias = Q + (size_t)K * K;
-    size_t moff = (size_t)(bias + 64 - ws);
-    moff = (moff + 15) / 16 * 16;                                      // 64-byte aligned mask words
-    unsigned long long* mask = reinterpret_cast<unsigned long long*>(ws + moff);
-    const int64_t npairs = (M / 2 + 66) / 2 * 2;                      // even (16-B aligned rows of words) + a tile of slack
-    BnwArgs a{g, y, scale, shift, act, mean, invstd, x, in_scale, in_shift, in_act, ws, mask, npairs, M, K, Nc, pl.rows_per_block, pl.TI};
+    const BnwWs l = bnw_ws(pl, M, K, Nc);
+    float *red = ws + l.red, *B1 = ws + l.B1, *Q = ws + l.Q, *bias = ws + l.bias;
+    unsigned long long* mask = reinterpret_cast<unsigned long long*>(ws + l.mask);
+    BnwArgs a{g, y, scale, shift, act, mean, invstd, x, in_scale, in_shift, in_act, ws, mask, l.npairs, M, K, Nc, pl.rows_per_block, pl.TI};
     dim3 grid(pl.splits, pl.nsl), block(256);
     switch (pl.TIs) {                       // <= 4 column tiles per slice (bnw_plan): <= 54 KB of dynamic LDS
         case 1: hipLaunchKernelGGL((pw_bnbwd_stage1b_kernel<1>), grid, block, pl.lds1, st, a); break;
@@ -3241,7 +3238,7 @@ static int pw_bnbwd_impl(const float* g, const float* y, const float* scale, con
     if (!allow_lds((const void*)pw_bnbwd_dgrad_kernel, 96 * 1024)) {
         set_error("pw_bnbwd: hipFuncSetAttribute failed"); return MNY_EHIP;
     }
-    BndArgs d{g, mask, act, x, in_scale, in_shift, in_act, B1, Q, bias, addend, dx, npairs, M, Nc, K, pl.TI, pl.m_tiles, pl.tiles_per_block,
+    BndArgs d{g, mask, act, x, in_scale, in_shift, in_act, B1, Q, bias, addend, dx, l.npairs, M, Nc, K, pl.TI, pl.m_tiles, pl.tiles_per_block,
               ry, r_scale, r_shift, r_mean, r_invstd, r_act, red_out};
     if (bnw_red_ok(M, K, Nc)) {                                    // second generation: barrier-free direct fragment loads (N % 16 == 0 instantiations)
         const int grid = bnw_red_grid(M);
@@ -3303,15 +3300,10 @@ extern "C" int mny_pw_bnbwd_bf16(const void* g, const void* y, const float* scal
         return pwe_launch(g, y, scale, shift, act, mean, invstd, gamma, x, in_scale, in_shift, in_act, w, addend, dx, dw, dgamma, dbeta, ws, M, K, Nc, st);
     BnwPlan pl = bnw_plan(M, K, Nc);
     const int64_t stride = bnw_stride(Nc, K);
-    float* red = ws + (size_t)pl.splits * stride;
-    float* B1 = red + stride;
-    float* Q = B1 + (size_t)Nc * K;
-    float* bias = Q + (size_t)K * K;
-    size_t moff = (size_t)(bias + 64 - ws);
-    moff = (moff + 15) / 16 * 16;
-    unsigned long long* mask = reinterpret_cast<unsigned long long*>(ws + moff);
-    const int64_t npairs = (M / 2 + 66) / 2 * 2;
-    BnwArgs a{(const float*)g, (const float*)y, scale, shift, act, mean, invstd, (const float*)x, in_scale, in_shift, in_act, ws, mask, npairs, M, K, Nc,
+    const BnwWs l = bnw_ws(pl, M, K, Nc);
+    float *red = ws + l.red, *B1 = ws + l.B1, *Q = ws + l.Q, *bias = ws + l.bias;
+    unsigned long long* mask = reinterpret_cast<unsigned long long*>(ws + l.mask);
+    BnwArgs a{(const float*)g, (const float*)y, scale, shift, act, mean, invstd, (const float*)x, in_scale, in_shift, in_act, ws, mask, l.npairs, M, K, Nc,
               pl.rows_per_block, pl.TI};
     dim3 grid(pl.splits, pl.nsl), block(256);
     // LDS: the bf16 ring is half the fp32 one, but the block reductions at the end use [3][16][64] + vector scratch in fp32
@@ -3332,7 +3324,7 @@ extern "C" int mny_pw_bnbwd_bf16(const void* g, const void* y, const float* scal
                        (double)M, Nc, K, dw, dgamma, dbeta, B1, Q, bias);
     rc = check_launch("pw_bnbwd_finalize_kernel");
     if (rc || !dx) return rc;
-    BndArgs d{(const float*)g, mask, act, (const float*)x, in_scale, in_shift, in_act, B1, Q, bias, (const float*)addend, (float*)dx, npairs, M, Nc, K, pl.TI,
+    BndArgs d{(const float*)g, mask, act, (const float*)x, in_scale, in_shift, in_act, B1, Q, bias, (const float*)addend, (float*)dx, l.npairs, M, Nc, K, pl.TI,
               pl.m_tiles, pl.tiles_per_block};
     const int grid2 = bnw_red_grid(M);
     switch (Nc) {

@@ -771,6 +771,89 @@ def test_dgrad_with_fused_bn_backward_reduction_bf16(ops, M, K, Nc, act, with_ad
     assert (s2 - (dz * xhat).sum(0)).abs().max().item() <= 2e-5 * (dz * xhat).abs().sum(0).max().item() + 1e-5
 
 
+_ROUTE_CASES = [    # smallest shapes that reach each kernel family; f: forward + statistics, d: data gradient + BN sums, p: both on weight planes, w: weight gradient
+    (torch.float32, "thin", 1000, 24, 144, "fd"), (torch.float32, "wide with a tail", 8209, 64, 384, "fd"), (torch.float32, "LDS-DMA fp32", 999, 40, 40, "fd"),
+    (torch.float32, "six-product", 1000, 128, 128, "fdp"), (torch.float32, "first generation", 500, 30, 36, "fw"),
+    (torch.float32, "stream weight gradient", 16384, 64, 384, "w"), (torch.bfloat16, "wave-16", 131072, 16, 64, "fd"),
+    (torch.bfloat16, "thin", 1000, 24, 144, "fd"), (torch.bfloat16, "LDS-DMA", 999, 64, 64, "fd"), (torch.bfloat16, "first generation", 500, 36, 40, "fw")]
+_ROUTE_FAMILY = {"thin": 3, "wide with a tail": 4, "LDS-DMA fp32": 1, "LDS-DMA": 1, "six-product": 2, "first generation": 0, "stream weight gradient": 5, "wave-16": 6}
+
+
+@pytest.mark.parametrize("dtype,family,M,K,Nc,what", _ROUTE_CASES, ids=["%s-%s" % (str(c[0])[6:], c[1].replace(" ", "_")) for c in _ROUTE_CASES])
+def test_pointwise_call_takes_the_predicted_family_and_writes_the_counted_rows(dtype, family, M, K, Nc, what):
+    """For a plain call (no view, bias or addend) of each kernel family: mny_pw_last_route afterwards equals mny_pw_route, and of a partial-row
+    buffer one row longer than the *_parts / *_splits query says (NaN-filled) exactly the counted rows are written — summing to the fp64 result
+    at the tolerance this file (tests/test_gpu_bf16.py for bf16 storage) uses for that family."""
+    import ctypes
+    from mobilenet_yolo_pytorch_amd import _lib
+    bf = dtype == torch.bfloat16
+    sfx = "_bf16" if bf else ""
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None            # noqa: E731
+    rows = lambda n, width: torch.full((n + 1, width), float("nan"), device="cuda")      # noqa: E731
+
+    def written(buf, n):
+        assert not torch.isnan(buf[:n]).any() and torch.isnan(buf[n]).all(), "%s: not exactly the %d counted rows were written" % (family, n)
+        return buf[:n].double()
+
+    rt, at = (2 ** -7, 2 ** -7) if bf else (2e-4, 2e-5)
+    x = rnd(M, K, seed=1).cuda().to(dtype)
+    w = (rnd(Nc, K, seed=2) * K ** -0.5).cuda().to(dtype)
+    xd, wd = x.double().cpu(), w.double().cpu()
+    want = xd @ wd.t()
+    op_family = lambda op: _lib.query("mny_pw_route", op, int(bf), M, K, Nc)             # noqa: E731
+    if "f" in what:
+        assert op_family(0) == _ROUTE_FAMILY[family]
+        parts = _lib.query("mny_pw_stat_parts" + sfx, M, K, Nc)
+        y, st = torch.empty(M, Nc, device="cuda", dtype=dtype), rows(parts, 2 * Nc)
+        _lib.call("mny_pw_fwd" + sfx, p(x), None, None, 0, p(w), None, None, p(y), p(st), M, K, Nc, stream)
+        assert _lib.query("mny_pw_last_route") == op_family(0)
+        check(y.float(), want, rt, at * want.abs().max().item() if bf else at, family + " fwd")
+        yd, s = y.double().cpu(), written(st, parts).view(parts, 2, Nc).sum(0).cpu()
+        check(s[0], yd.sum(0), 1e-4, 2e-3, family + " stats sum")                          # over the STORED values
+        check(s[1], (yd ** 2).sum(0), 1e-4, 2e-3, family + " stats sumsq")
+    if "d" in what:             # x plays dy: [M, K] -> dx [M, Nc] with W^T rows [Nc][K] = w
+        assert op_family(1) == _ROUTE_FAMILY[family]
+        yraw = (rnd(M, Nc, seed=3) * 2).cuda().to(dtype)
+        c = [(1 + 0.3 * rnd(Nc, seed=4)).cuda(), (0.5 * rnd(Nc, seed=5)).cuda(), (0.2 * rnd(Nc, seed=6)).cuda(), (1 + 0.2 * rnd(Nc, seed=7).abs()).cuda()]
+        xhat = (yraw.double().cpu() - c[2].double().cpu()) * c[3].double().cpu()
+        assert _lib.query("mny_pw_dgrad_bnred_supported" + sfx, M, K, Nc, 0) == 1
+        rparts = _lib.query("mny_pw_dgrad_bnred_parts" + sfx, M, K, Nc)
+        dx, red = torch.empty(M, Nc, device="cuda", dtype=dtype), rows(rparts, 2 * Nc)
+        _lib.call("mny_pw_dgrad_bnred" + sfx, p(x), p(w), p(dx), p(yraw), p(c[0]), p(c[1]), 0, p(c[2]), p(c[3]), p(red), M, K, Nc, stream)
+        assert _lib.query("mny_pw_last_route") == op_family(1)
+        check(dx.float(), want, rt, at * want.abs().max().item() if bf else at, family + " dgrad")
+        dz, r = dx.double().cpu(), written(red, rparts).view(rparts, 2, Nc).sum(0).cpu()     # identity activation: dz = the stored dx
+        assert (r[0] - dz.sum(0)).abs().max().item() <= 2e-5 * dz.abs().sum(0).max().item() + 1e-5
+        assert (r[1] - (dz * xhat).sum(0)).abs().max().item() <= 2e-5 * (dz * xhat).abs().sum(0).max().item() + 1e-5
+    if "p" in what:             # the same two calls on pre-cut weight planes: same family, same rows, same arithmetic
+        assert _lib.query("mny_pw_w6_supported", M, K, Nc) == 1
+        w6, = _cut3([w])
+        y6, st6 = torch.empty(M, Nc, device="cuda"), rows(parts, 2 * Nc)
+        _lib.call("mny_pw_fwd_w6", p(x), None, None, 0, p(w6), None, None, p(y6), p(st6), M, K, Nc, stream)
+        assert _lib.query("mny_pw_last_route") == op_family(0)
+        assert torch.equal(y6, y) and torch.equal(written(st6, parts), st[:parts].double())
+        dx6, red6 = torch.empty(M, Nc, device="cuda"), rows(rparts, 2 * Nc)
+        _lib.call("mny_pw_dgrad_bnred_w6", p(x), p(w6), None, p(dx6), p(yraw), p(c[0]), p(c[1]), 0, p(c[2]), p(c[3]), p(red6), M, K, Nc, stream)
+        assert _lib.query("mny_pw_last_route") == op_family(1)
+        assert torch.equal(dx6, dx) and torch.equal(written(red6, rparts), red[:rparts].double())
+    if "w" in what:             # partial rows [splits][Nc][K], the deferred-combine form (dw == NULL)
+        assert op_family(2) == _ROUTE_FAMILY[family]
+        dy = rnd(M, Nc, seed=9).cuda().to(dtype)
+        splits = _lib.query("mny_pw_wgrad_splits" + sfx, M, K, Nc)
+        ws = rows(splits, Nc * K)
+        _lib.call("mny_pw_wgrad" + sfx, p(x), None, None, 0, p(dy), None, None, p(ws), M, K, Nc, stream)
+        assert _lib.query("mny_pw_last_route") == op_family(2)
+        ref = dy.double().cpu().t() @ xd
+        got = written(ws, splits).sum(0).view(Nc, K).cpu()
+        if family == "stream weight gradient":
+            assert (got - ref).abs().max().item() <= 2e-5 * ref.abs().max().item()
+        elif bf:
+            check(got, ref, 3e-4, 3e-4 * max(1.0, ref.abs().max().item()), family + " wgrad")
+        else:
+            check(got, ref, 2e-4, 2e-4, family + " wgrad")
+
+
 @pytest.mark.parametrize("M,K,Nc,act,dtype", [
     (200003, 24, 144, 1, torch.float32), (150001, 16, 96, 1, torch.float32), (99999, 32, 192, 1, torch.float32), (130007, 32, 16, 0, torch.float32),
     (70001, 8, 20, 2, torch.float32), (50000, 16, 256, 4, torch.float32), (1, 24, 16, 3, torch.float32), (127, 32, 252, 1, torch.float32),

@@ -191,8 +191,9 @@ def test_mbv3_eval_mode_losses_are_differentiable_frozen_batchnorm():
 
 def test_recorded_kernel_routes_are_what_the_dispatchers_did():
     """NetPlan.kernel_routes() reports the family each pointwise-conv call's dispatcher TOOK at the plan's first replay
-    (mny_pw_last_route), not a prediction: MobileNetV3's weight gradients over h-swish views run the register-staged kernel in fp32
-    (pw_wgrad_impl keeps them off the LDS-DMA kernels) although the plain-view predictor mny_pw_route says otherwise."""
+    (mny_pw_last_route), not the family of another call: MobileNetV3's weight gradients over h-swish views run the register-staged kernel
+    in fp32 (the weight-gradient route keeps that view off the LDS-DMA kernels), while mny_pw_route answers for the same shape behind a plain
+    view — the same rule, asked about a different call."""
     from mobilenet_yolo_pytorch_amd import _lib
     m = _model(True)
     x = procedural.images(2, 256, 256, seed=3).cuda()
@@ -208,4 +209,4 @@ def test_recorded_kernel_routes_are_what_the_dispatchers_did():
         n_diff += int(fam != _lib.query("mny_pw_route", op, 0, M, K, N))
         assert 0 <= fam <= 5
     hsw = [nd for nd in m.graph.nodes if nd.op == "pw" and nd.ins[0].act == _lib.ACT_HSWISH]
-    assert hsw and n_diff > 0           # at least the h-swish-view weight gradients differ from the plain-view prediction
+    assert hsw and n_diff > 0           # at least the h-swish-view weight gradients differ from the plain-view answer
