@@ -369,6 +369,29 @@ typedef struct mny_adamw_chunk {
 int mny_adamw_step(const mny_adamw_chunk* table_dev, int nchunks, double lr, double beta1, double beta2, double eps,
                    double weight_decay, int64_t step, void* stream);
 
+/* ---- fused multi-tensor SGD, weight EMA and shadow swap (no reference counterpart beyond train.py:457's --momentum) --
+ * The same DEVICE chunk table and launch shape as mny_adamw_step (one workgroup per chunk of the caller's length, float4
+ * body, scalar tail); each entry point reads only the fields listed, and `vec4` means "every pointer THIS entry point
+ * uses is 16-B aligned".  Scalars are derived in double and rounded to float once.  No float atomics: deterministic.
+ *
+ * mny_sgd_step — torch.optim.SGD(maximize=False).step().  Reads p, g, n, vec4, and m when momentum != 0 (m may be
+ *   NULL otherwise: it is neither read nor written); v is unused.  Per element
+ *       d = g + weight_decay * p                                      (skipped exactly when weight_decay == 0)
+ *       momentum != 0:  buf = d when `first`, else momentum * buf + (1 - dampening) * d       (buf = m, written back)
+ *                       d = nesterov ? d + momentum * buf : buf
+ *       p -= lr * d
+ *   `first` = these chunks have no momentum buffer yet (torch's `momentum_buffer is None`): m is only written.
+ * mny_ema_update — m <- m + (1 - decay) * (p - m), torch.lerp's form for a weight below 0.5 (one fmaf).  Reads p
+ *   (read only), m, n, vec4; g and v are unused.
+ * mny_swap_chunks — exchanges p[0..n) and m[0..n) exactly; two calls are the identity bit for bit.  Reads p, m, n,
+ *   vec4; g and v are unused.
+ * MNY_EINVAL (before any launch): null table or nchunks <= 0; negative (or NaN) lr, momentum, weight_decay; nesterov
+ * with momentum <= 0 or dampening != 0 (torch's ValueError); decay outside [0, 1] (NaN included).                 */
+int mny_sgd_step(const mny_adamw_chunk* table_dev, int nchunks, double lr, double momentum, double dampening,
+                 double weight_decay, int nesterov, int first, void* stream);
+int mny_ema_update(const mny_adamw_chunk* table_dev, int nchunks, double decay, void* stream);
+int mny_swap_chunks(const mny_adamw_chunk* table_dev, int nchunks, void* stream);
+
 /* ---- fused gradient clipping (torch.nn.utils.clip_grad_norm_, L2, in two launches) ----------------------------
  * `segs_dev` is a DEVICE array of gradient segments: g[0..n) fp32, 4-byte aligned, any n >= 0.  A segment of n floats
  * is cut into mny_grad_clip_parts(n) blocks of MNY_CLIP_BLOCK floats; `block0` is the number of blocks of the

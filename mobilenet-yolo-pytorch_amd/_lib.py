@@ -67,6 +67,9 @@ _SIGS = {
     "mny_stemdw_bwd_ws_floats": (c_size_t, [c_int] * 4),
     "mny_stemdw_bwd": (c_int, [P, P, P, P, c_int, P, P, P, P, P, P, P, c_int, P, P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, P]),
     "mny_adamw_step": (c_int, [P, c_int, c_double, c_double, c_double, c_double, c_double, c_int64, P]),
+    "mny_sgd_step": (c_int, [P, c_int, c_double, c_double, c_double, c_double, c_int, c_int, P]),
+    "mny_ema_update": (c_int, [P, c_int, c_double, P]),
+    "mny_swap_chunks": (c_int, [P, c_int, P]),
     "mny_grad_clip_parts": (c_int, [c_int64]),
     "mny_grad_clip": (c_int, [P, c_int, c_int, c_double, P, P, P]),
     "mny_pw_fwd": (c_int, [P, P, P, c_int, P, P, P, P, P, c_int64, c_int, c_int, P]),

@@ -7,6 +7,7 @@
 // (amsgrad = False, maximize = False; the caller passes the two bias corrections, so `step` stays on the host).
 // HBM-bound: 4 reads + 3 writes of 4 B per parameter (4.9 M parameters -> 138 MB, ~30 us), against 202 small launches upstream.
 // The chunk table lives in device memory and is built once per model (parameter / gradient-arena / state pointers are stable).
+// Further down, on the same chunk rows: fused SGD with momentum, the weight EMA and the shadow <-> weights swap.
 #include "common.h"
 
 namespace mny {
@@ -126,6 +127,99 @@ __global__ __launch_bounds__(256) void clip_scale_kernel(const mny_clip_seg* __r
     if (t < sp.cnt - ts) sp.g[ts + t] *= coef;
 }
 
+// ---- fused multi-tensor SGD (mny_sgd_step), weight EMA (mny_ema_update) and the shadow swap (mny_swap_chunks) ----
+// The same chunk rows and launch shape as adamw_kernel: one workgroup per chunk, float4 body, scalar tail.  HBM-bound streams:
+// SGD with momentum 3 reads + 2 writes of 4 B per element, the EMA 2 reads + 1 write, the swap 2 + 2.
+// Every product-sum is written as the fmaf torch's own kernels contract to (`add(other, alpha)` is one a + alpha*b):
+//     d = g + wd*p ; buf = (mu*buf) + (1-damp)*d ; d = d + mu*buf ; p = p + (-lr)*d
+// WD: weight_decay != 0.  MOM: 0 = no momentum (ch.m is NULL and never touched), 1 = first step (buf = d, ch.m written only), 2 = running.
+template <bool WD, int MOM, bool NEST>
+__global__ __launch_bounds__(256) void sgd_kernel(const mny_adamw_chunk* __restrict__ table, int nchunks, float neg_lr, float mu, float omd, float wd) {
+    const int ci = blockIdx.x;
+    if (ci >= nchunks) return;
+    const mny_adamw_chunk ch = table[ci];
+    float* __restrict__ p = ch.p;
+    const float* __restrict__ g = ch.g;
+    float* __restrict__ m = ch.m;
+    auto upd = [&](float pv, float gv, float& mv) {
+        float d = WD ? fmaf(wd, pv, gv) : gv;
+        if (MOM == 1) mv = d;
+        if (MOM == 2) mv = fmaf(omd, d, mu * mv);
+        if (MOM != 0) d = NEST ? fmaf(mu, mv, d) : mv;
+        return fmaf(neg_lr, d, pv);
+    };
+    const int n4 = ch.vec4 ? ch.n / 4 : 0;
+    for (int i = threadIdx.x; i < n4; i += 256) {
+        float4 pv = ld4(p + 4 * i), mv = make_float4(0.f, 0.f, 0.f, 0.f);
+        const float4 gv = ld4(g + 4 * i);
+        if (MOM == 2) mv = ld4(m + 4 * i);
+        pv.x = upd(pv.x, gv.x, mv.x); pv.y = upd(pv.y, gv.y, mv.y);
+        pv.z = upd(pv.z, gv.z, mv.z); pv.w = upd(pv.w, gv.w, mv.w);
+        st4(p + 4 * i, pv);
+        if (MOM != 0) st4(m + 4 * i, mv);
+    }
+    for (int i = n4 * 4 + threadIdx.x; i < ch.n; i += 256) {
+        float mv = MOM == 2 ? m[i] : 0.f;
+        p[i] = upd(p[i], g[i], mv);
+        if (MOM != 0) m[i] = mv;
+    }
+}
+
+// m <- m + (1 - decay) * (p - m): torch.lerp for a weight below 0.5, one fmaf.  p is read only.
+__global__ __launch_bounds__(256) void ema_kernel(const mny_adamw_chunk* __restrict__ table, int nchunks, float omd) {
+    const int ci = blockIdx.x;
+    if (ci >= nchunks) return;
+    const mny_adamw_chunk ch = table[ci];
+    const float* __restrict__ p = ch.p;
+    float* __restrict__ m = ch.m;
+    const int n4 = ch.vec4 ? ch.n / 4 : 0;
+    for (int i = threadIdx.x; i < n4; i += 256) {
+        const float4 pv = ld4(p + 4 * i);
+        float4 mv = ld4(m + 4 * i);
+        mv.x = fmaf(omd, pv.x - mv.x, mv.x); mv.y = fmaf(omd, pv.y - mv.y, mv.y);
+        mv.z = fmaf(omd, pv.z - mv.z, mv.z); mv.w = fmaf(omd, pv.w - mv.w, mv.w);
+        st4(m + 4 * i, mv);
+    }
+    for (int i = n4 * 4 + threadIdx.x; i < ch.n; i += 256) {
+        const float mv = m[i];
+        m[i] = fmaf(omd, p[i] - mv, mv);
+    }
+}
+
+// p[0..n) <-> m[0..n): every element is read and written by one thread, so the exchange is exact and two calls are the identity
+__global__ __launch_bounds__(256) void swap_kernel(const mny_adamw_chunk* __restrict__ table, int nchunks) {
+    const int ci = blockIdx.x;
+    if (ci >= nchunks) return;
+    const mny_adamw_chunk ch = table[ci];
+    float* __restrict__ p = ch.p;
+    float* __restrict__ m = ch.m;
+    const int n4 = ch.vec4 ? ch.n / 4 : 0;
+    for (int i = threadIdx.x; i < n4; i += 256) {
+        const float4 pv = ld4(p + 4 * i), mv = ld4(m + 4 * i);
+        st4(p + 4 * i, mv); st4(m + 4 * i, pv);
+    }
+    for (int i = n4 * 4 + threadIdx.x; i < ch.n; i += 256) {
+        const float pv = p[i];
+        p[i] = m[i];
+        m[i] = pv;
+    }
+}
+
+template <bool WD, int MOM, bool NEST>
+static int sgd_launch(const mny_adamw_chunk* table, int nchunks, float neg_lr, float mu, float omd, float wd, hipStream_t stream) {
+    hipLaunchKernelGGL((sgd_kernel<WD, MOM, NEST>), dim3(nchunks), dim3(256), 0, stream, table, nchunks, neg_lr, mu, omd, wd);
+    return check_launch("sgd_kernel");
+}
+
+template <bool WD>
+static int sgd_pick(int mom, bool nest, const mny_adamw_chunk* table, int nchunks, float neg_lr, float mu, float omd, float wd, hipStream_t stream) {
+    if (mom == 0) return sgd_launch<WD, 0, false>(table, nchunks, neg_lr, mu, omd, wd, stream);
+    if (mom == 1) return nest ? sgd_launch<WD, 1, true>(table, nchunks, neg_lr, mu, omd, wd, stream)
+                              : sgd_launch<WD, 1, false>(table, nchunks, neg_lr, mu, omd, wd, stream);
+    return nest ? sgd_launch<WD, 2, true>(table, nchunks, neg_lr, mu, omd, wd, stream)
+                : sgd_launch<WD, 2, false>(table, nchunks, neg_lr, mu, omd, wd, stream);
+}
+
 }  // namespace mny
 
 using namespace mny;
@@ -154,4 +248,28 @@ extern "C" int mny_grad_clip(const mny_clip_seg* segs_dev, int nsegs, int nblock
     if (int rc = check_launch("clip_sumsq_kernel")) return rc;
     hipLaunchKernelGGL(clip_scale_kernel, dim3(nblocks), dim3(256), 0, (hipStream_t)stream, segs_dev, nsegs, ws, nblocks, (float)max_norm, out);
     return check_launch("clip_scale_kernel");
+}
+
+extern "C" int mny_sgd_step(const mny_adamw_chunk* table_dev, int nchunks, double lr, double momentum, double dampening, double weight_decay,
+                            int nesterov, int first, void* stream) {
+    MNY_REQUIRE(table_dev && nchunks > 0, "sgd_step: bad arguments");
+    MNY_REQUIRE(lr >= 0.0 && momentum >= 0.0 && weight_decay >= 0.0, "sgd_step: lr, momentum and weight_decay must be >= 0");      // (NaN fails too)
+    MNY_REQUIRE(!nesterov || (momentum > 0.0 && dampening == 0.0), "sgd_step: nesterov momentum requires a momentum and zero dampening");
+    const int mom = momentum == 0.0 ? 0 : (first ? 1 : 2);
+    const float neg_lr = (float)-lr, mu = (float)momentum, omd = (float)(1.0 - dampening), wd = (float)weight_decay;
+    return weight_decay != 0.0 ? sgd_pick<true>(mom, nesterov != 0, table_dev, nchunks, neg_lr, mu, omd, wd, (hipStream_t)stream)
+                               : sgd_pick<false>(mom, nesterov != 0, table_dev, nchunks, neg_lr, mu, omd, wd, (hipStream_t)stream);
+}
+
+extern "C" int mny_ema_update(const mny_adamw_chunk* table_dev, int nchunks, double decay, void* stream) {
+    MNY_REQUIRE(table_dev && nchunks > 0, "ema_update: bad arguments");
+    MNY_REQUIRE(decay >= 0.0 && decay <= 1.0, "ema_update: decay must be in [0,1]");                                                 // (NaN fails too)
+    hipLaunchKernelGGL(ema_kernel, dim3(nchunks), dim3(256), 0, (hipStream_t)stream, table_dev, nchunks, (float)(1.0 - decay));
+    return check_launch("ema_kernel");
+}
+
+extern "C" int mny_swap_chunks(const mny_adamw_chunk* table_dev, int nchunks, void* stream) {
+    MNY_REQUIRE(table_dev && nchunks > 0, "swap_chunks: bad arguments");
+    hipLaunchKernelGGL(swap_kernel, dim3(nchunks), dim3(256), 0, (hipStream_t)stream, table_dev, nchunks);
+    return check_launch("swap_kernel");
 }
