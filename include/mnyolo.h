@@ -621,6 +621,60 @@ int mny_aug_seg_batch(const uint8_t* seg_src, const int64_t* seg_offsets, const 
                       const mny_aug_sample* samples, int n_out, int n_classes, int max_in_h, int max_in_w, int out_h,
                       int out_w, float* out, void* ws, void* stream);
 
+/* ---- the loader's blur / sharpen / noise stage (csrc/augseq.hip) ----------------------------------------------
+ * The reference runs imgaug's `seq` (folder2lmdb.py:28-42) on every decoded image before transform_od (:131):
+ * Sometimes(0.5, SomeOf((1, 2), [OneOf([GaussianBlur(0..1), MedianBlur(3..5)]), Sharpen(alpha 0..0.1, lightness
+ * 0.9..1.1), AdditiveGaussianNoise(scale 0..0.03*255, per_channel 0.3)], random_order)).  The host makes the draws
+ * (augment.py SeqAugment.plan); the device applies zero, one or two ops per image, uint8 -> uint8, the second op
+ * reading the first one's uint8 result.  imgaug and cv2 are restated, not linked: this stage is parity-unpinned
+ * against them and the arithmetic below IS the specification (tests/seq_ref.py holds it in numpy/scipy, fp64).
+ * With p the centre pixel, per channel:
+ *   MNY_SEQ_GAUSS    5x5 separable (imgaug's size for sigma <= 1 is max(int(3.3 sigma), 5) = 5).  taps[d+2] =
+ *                    exp(-d^2 / 2 sigma^2), d = -2..2, normalised in fp64 and cast to fp32 by the host.  Horizontal
+ *                    pass sum_d taps[d] * p in fp32, in tap order, kept unrounded; vertical pass the same; rintf,
+ *                    clamp to 0..255.  Border REFLECT_101 (dcb|abcd|cba), iterated, so that sides of 1 and 2 work
+ *                    (a side of 1 reads index 0).  sigma < 1e-3 is the identity: the host emits no op.
+ *   MNY_SEQ_MEDIAN   median_k x median_k, median_k 3 or 5, border REPLICATE, exact.
+ *   MNY_SEQ_SHARPEN  rintf(sharpen_c * p + sharpen_s * S8) clamped to 0..255, S8 the integer sum of the eight
+ *                    neighbours under REFLECT_101; the two products and the sum are fp32 operations of their own (no
+ *                    FMA).  Host: sharpen_c = (1 - alpha) + alpha * (8 + lightness), sharpen_s = -alpha in fp64, cast
+ *                    to fp32; alpha = 0 is exactly the identity.
+ *   MNY_SEQ_NOISE    Philox4x32-10 as published, key = noise_key, counter = (y * w + x, 0, 0, 0); its outputs r0..r3
+ *                    give u_i = ((float)(r_i >> 8) + 0.5f) * 2^-24 (in (0, 1]; exact below 2^23, else rounded to
+ *                    fp32); z0 = R(u0) cos(2 pi u1), z1 = R(u0) sin(2 pi u1), z2 = R(u2) cos(2 pi u3), R(u) =
+ *                    sqrtf(-2 logf(u)), accurate fp32 library functions.  noise_per_channel: the channels take z0,
+ *                    z1, z2, otherwise all three take z0.  out = clamp(p + (int)rintf(noise_scale * z), 0, 255).
+ * src: decoded RGB uint8 images, HWC, packed in one DEVICE buffer; desc (DEVICE, [n_items]): offset (a multiple of
+ * 4) and size of each, 3 * h * w bytes; seq (DEVICE, [n_items]): one record per image.  dst is laid out like src
+ * (dst != src; src, dst and ws 4-byte aligned): after the call it holds EVERY image, one with n_ops == 0 copied byte
+ * for byte; bytes between and after the images are not written.  Nothing is read past an image's 3 * h * w bytes.
+ * max_in_h / max_in_w: the caller's bounds on the image sizes (at most 16383); n_items at most 4096.
+ * The int32 at ws+0 receives 0, or 1 + the lowest index of an item that is outside the bounds or misaligned, has
+ * n_ops outside 0..2, an unknown or a repeated op, a median size other than 3 or 5, or a non-finite coefficient of
+ * an op it uses.  Such an image is written as zeros (an item with a negative offset or a side outside 1..16383
+ * names no bytes and is only reported); nothing outside its 3 * h * w bytes is touched.
+ * ws: mny_aug_seq_ws_bytes() (0 = bad arguments; src_bytes = the size of src).  The two-op images pass through ws:
+ * after the call ws + 256 + offset holds op 0's uint8 result of each of them.
+ * Two launches, no host sync, no allocation, no atomics; deterministic launch to launch. */
+#define MNY_SEQ_GAUSS 0
+#define MNY_SEQ_MEDIAN 1
+#define MNY_SEQ_SHARPEN 2
+#define MNY_SEQ_NOISE 3
+typedef struct mny_aug_seq_item {
+    int32_t n_ops; /* 0..2 */
+    int32_t op[2]; /* MNY_SEQ_*, in application order, no kind twice */
+    float taps[5];
+    int32_t median_k;
+    float sharpen_c, sharpen_s;
+    float noise_scale;
+    int32_t noise_per_channel;
+    uint32_t noise_key[2];
+    int32_t reserved;
+} mny_aug_seq_item; /* 64 bytes */
+size_t mny_aug_seq_ws_bytes(int n_items, int64_t src_bytes, int max_in_h, int max_in_w);
+int mny_aug_seq_batch(const uint8_t* src, const mny_image_desc* desc, const mny_aug_seq_item* seq, int n_items,
+                      int max_in_h, int max_in_w, uint8_t* dst, void* ws, void* stream);
+
 /* ---- bf16 STORAGE twins (BASELINE config 4: MobileNetV3-YOLO 512x512 bf16) -----------------
  * Every `mny_X_bf16` has the contract of `mny_X` above with ONE difference: the activation-sized tensors (the
  * `void*` parameters: raw conv outputs, materialised sums, gradients wrt activations) are bf16 in HBM.  Kernels

@@ -14,10 +14,19 @@ those of a plain instance) and `mny_aug_seg_batch` builds collate_fn's per-class
 (folder2lmdb.py:135-141,243-261).  The geometry is pinned to the reference; the cv2 INTER_AREA resize is restated from
 OpenCV's source (cv2 is not available to pin it), see include/mnyolo.h.  The reference defines no Mosaic with seg maps.
 
-Not covered (stays with the caller): imgaug's `seq` (folder2lmdb.py:28-42, applied to the decoded image before this
-stage, which is the reference's order too), JPEG decoding, the sampler, and the scale < 1 path of the area resize (a
-cropped geometry smaller than the S/16 grid is refused).  No CPU fallback: without libmnyolo.so every call raises
-MnyError."""
+`SeqAugment` is the stage in front of all that: imgaug's `seq` (folder2lmdb.py:28-42), which the reference runs on every
+decoded image before `transform_od` (:131): with probability 0.5 one or two of {Gaussian or median blur, sharpen, additive
+Gaussian noise} in random order.  `SeqAugment.plan` draws from a numpy Generator of its own (imgaug does too; Python's
+`random` is never touched, so TrainAugment's draws are those of a seq-less instance) and `mny_aug_seq_batch`
+(csrc/augseq.hip) applies the ops uint8 -> uint8 on the packed upload; `TrainAugment(..., seq=SeqAugment(seed))` runs it
+between the upload and `mny_aug_batch`.  Neither imgaug nor cv2 is available to pin it: like the INTER_AREA resize this
+stage is parity-unpinned against the third-party libraries, the arithmetic stated in include/mnyolo.h is the specification
+(tests/seq_ref.py restates it with numpy and scipy).  The reference applies `seq` in the test phase as well (line 131 has
+no phase check); `SeqAugment.run_device` in front of `BatchPrep.run_device` reproduces that quirk for whoever wants it, it
+is not a default.
+
+Not covered (stays with the caller): JPEG decoding, the sampler, and the scale < 1 path of the area resize (a cropped
+geometry smaller than the S/16 grid is refused).  No CPU fallback: without libmnyolo.so every call raises MnyError."""
 import ctypes
 import math
 import random
@@ -26,7 +35,7 @@ import numpy as np
 import torch
 
 from ._lib import call, query
-from .prep import BatchPrep
+from .prep import DESC, BatchPrep
 
 BRIGHTNESS, CONTRAST, SATURATION, HUE, GAMMA = range(5)      # MNY_AUG_*; image_augmentation.py:178-182 order
 
@@ -37,6 +46,12 @@ ITEM = np.dtype([("offset", np.int64), ("h", np.int32), ("w", np.int32), ("n_ops
 SAMPLE = np.dtype([("first_item", np.int32), ("n_items", np.int32), ("canvas_slot", np.int32), ("reserved", np.int32)])
 assert ITEM.itemsize == 392 and SAMPLE.itemsize == 16
 SEG_MAX_CLASSES = 8                                           # MNY_AUG_SEG_MAX_CLASSES
+SEQ_GAUSS, SEQ_MEDIAN, SEQ_SHARPEN, SEQ_NOISE = range(4)      # MNY_SEQ_*
+SEQ = np.dtype([("n_ops", np.int32), ("op", np.int32, 2), ("taps", np.float32, 5), ("median_k", np.int32), ("sharpen_c", np.float32),
+                ("sharpen_s", np.float32), ("noise_scale", np.float32), ("noise_per_channel", np.int32), ("noise_key", np.uint32, 2),
+                ("reserved", np.int32)])                                                          # mny_aug_seq_item
+assert SEQ.itemsize == 64
+SEQ_SIGMA_MIN = 1e-3                                          # imgaug GaussianBlur: a sigma below this is the identity
 
 
 def hue_shift_u8(f):
@@ -60,6 +75,148 @@ def _jaccard(set_1, set_2):
     return inter / (a1.unsqueeze(1) + a2.unsqueeze(0) - inter)
 
 
+def gauss_taps(sigma):
+    """The five taps exp(-d^2 / 2 sigma^2), d = -2..2, normalised in fp64, as fp32."""
+    d = np.arange(-2, 3, dtype=np.float64)
+    t = np.exp(-d * d / (2.0 * float(sigma) ** 2))
+    return (t / t.sum()).astype(np.float32)
+
+
+def sharpen_coeffs(alpha, lightness):
+    """imgaug Sharpen: (1 - alpha) * identity + alpha * [[-1,-1,-1],[-1,8+l,-1],[-1,-1,-1]] -> (centre, neighbour) as fp32."""
+    a, l = float(alpha), float(lightness)
+    return np.float32((1.0 - a) + a * (8.0 + l)), np.float32(-a)
+
+
+def seq_records(op_lists):
+    """Per image a list of at most two ops -> SEQ array.  An op is (SEQ_GAUSS, sigma), (SEQ_MEDIAN, k), (SEQ_SHARPEN, alpha,
+    lightness) or (SEQ_NOISE, scale, per_channel, key); a Gaussian with sigma < 1e-3 is the identity and is dropped."""
+    rec = np.zeros(len(op_lists), SEQ)
+    rec["median_k"] = 3
+    for r, ops in zip(rec, op_lists):
+        ops = [o for o in ops if not (o[0] == SEQ_GAUSS and o[1] < SEQ_SIGMA_MIN)]
+        if len(ops) > 2 or len({o[0] for o in ops}) != len(ops):
+            raise ValueError("an image takes at most two ops of different kinds, got %r" % (ops,))
+        r["n_ops"] = len(ops)
+        for k, o in enumerate(ops):
+            r["op"][k] = o[0]
+            if o[0] == SEQ_GAUSS:
+                r["taps"] = gauss_taps(o[1])
+            elif o[0] == SEQ_MEDIAN:
+                if o[1] not in (3, 5):
+                    raise ValueError("median size must be 3 or 5, got %r" % (o[1],))
+                r["median_k"] = o[1]
+            elif o[0] == SEQ_SHARPEN:
+                r["sharpen_c"], r["sharpen_s"] = sharpen_coeffs(o[1], o[2])
+            elif o[0] == SEQ_NOISE:
+                r["noise_scale"], r["noise_per_channel"] = o[1], int(bool(o[2]))
+                r["noise_key"] = (int(o[3]) & 0xffffffff, (int(o[3]) >> 32) & 0xffffffff)
+            else:
+                raise ValueError("unknown op %r" % (o[0],))
+    return rec
+
+
+class SeqAugment:
+    """seq = SeqAugment(seed)                       # the reference's imgaug `seq`, folder2lmdb.py:28-42
+       dst = seq.run_device(src, desc, seq.plan(len(desc)))     # src: the packed uint8 upload; dst: the same layout
+    or TrainAugment(..., seq=seq), which does exactly that between the upload and mny_aug_batch.  The draws come from a
+    numpy Generator owned by the instance, never from Python's `random`.  Per image, each draw a vector over the batch, in
+    this order: (1) gate < p; (2) count in {1, 2}; (3) a permutation of the children (blur, sharpen, noise), the first
+    `count` run in that order; (4) blur kind, Gaussian or median at 1/2 each; (5) sigma ~ U(0, 1), then k from {3, 4, 5}
+    with an even draw raised to the next odd (imgaug MedianBlur); (6) alpha ~ U(0, 0.1); (7) lightness ~ U(0.9, 1.1); (8) the
+    per-channel flag at 0.3; (9) scale ~ U(0, 0.03 * 255); (10) a 64-bit noise key.  Every vector is drawn whether or not an
+    image uses it, so plan() is a function of the seed and the batch sizes alone."""
+    CHILDREN = ("blur", "sharpen", "noise")
+
+    def __init__(self, seed=None, p=0.5, device="cuda:0"):
+        self.gen = np.random.Generator(np.random.PCG64(seed))
+        self.p = float(p)
+        self.device = torch.device(device)
+        self._fixed = None
+        self._status = None
+
+    @classmethod
+    def fixed(cls, records, device="cuda:0"):
+        """Explicit per-image ops in place of the draws: a SEQ array or the op lists seq_records() takes."""
+        self = cls(0, device=device)
+        self._fixed = records.copy() if isinstance(records, np.ndarray) and records.dtype == SEQ else seq_records(records)
+        return self
+
+    def draw(self, n_images):
+        """The raw draws of one batch, in the documented order (host only)."""
+        g, n = self.gen, int(n_images)
+        d = dict(gate=g.random(n) < self.p)
+        d["count"] = g.integers(1, 3, n)
+        d["order"] = np.argsort(g.random((n, 3)), axis=1)
+        d["gauss"] = g.random(n) < 0.5
+        d["sigma"] = g.uniform(0.0, 1.0, n)
+        k = g.integers(3, 6, n)
+        d["k"] = k + (k % 2 == 0)
+        d["alpha"] = g.uniform(0.0, 0.1, n)
+        d["lightness"] = g.uniform(0.9, 1.1, n)
+        d["per_channel"] = g.random(n) < 0.3
+        d["scale"] = g.uniform(0.0, 0.03 * 255, n)
+        d["key"] = g.integers(0, 2 ** 64, n, dtype=np.uint64)
+        return d
+
+    @staticmethod
+    def records(d):
+        """draw() -> SEQ array."""
+        ops = []
+        for i in range(len(d["gate"])):
+            chain = []
+            if d["gate"][i]:
+                for child in d["order"][i][:d["count"][i]]:
+                    if child == 0:
+                        chain.append((SEQ_GAUSS, float(d["sigma"][i])) if d["gauss"][i] else (SEQ_MEDIAN, int(d["k"][i])))
+                    elif child == 1:
+                        chain.append((SEQ_SHARPEN, float(d["alpha"][i]), float(d["lightness"][i])))
+                    else:
+                        chain.append((SEQ_NOISE, float(d["scale"][i]), bool(d["per_channel"][i]), int(d["key"][i])))
+            ops.append(chain)
+        return seq_records(ops)
+
+    def plan(self, n_images):
+        """Host only: the SEQ record of each of the batch's n_images decoded images."""
+        if self._fixed is not None:
+            if len(self._fixed) != n_images:
+                raise ValueError("fixed records describe %d images, the batch holds %d" % (len(self._fixed), n_images))
+            return self._fixed
+        return self.records(self.draw(n_images))
+
+    def run_device(self, src, desc_or_items, plan):
+        """src: the packed uint8 images on the device; desc_or_items: their DESC array (prep.py) or TrainAugment's ITEM array with
+        the offsets set; plan: plan(len(desc)).  -> dst, laid out like src, every image in it."""
+        n = len(desc_or_items)
+        if len(plan) != n or plan.dtype != SEQ:
+            raise ValueError("the plan must hold one SEQ record per image")
+        desc = np.zeros(n, DESC)
+        for f in ("offset", "h", "w"):
+            desc[f] = desc_or_items[f]
+        max_h, max_w = int(desc["h"].max()), int(desc["w"].max())
+        nbytes = int(src.numel())
+        size = query("mny_aug_seq_ws_bytes", n, nbytes, max_h, max_w)
+        if size == 0:
+            raise ValueError("mny_aug_seq_ws_bytes refused n=%d bytes=%d max %dx%d" % (n, nbytes, max_h, max_w))
+        dev = src.device                                       # the stage runs where the upload is
+        ws = torch.empty(size, device=dev, dtype=torch.uint8)
+        dst = torch.empty_like(src)
+        d_dev = torch.from_numpy(desc.view(np.uint8).copy()).to(dev, non_blocking=True)
+        s_dev = torch.from_numpy(np.ascontiguousarray(plan).view(np.uint8).copy()).to(dev, non_blocking=True)
+        p = lambda t: ctypes.c_void_p(t.data_ptr())
+        call("mny_aug_seq_batch", p(src), p(d_dev), p(s_dev), n, max_h, max_w, p(dst), p(ws), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+        self._status = ws[:4].view(torch.int32)
+        self._keep = (src, d_dev, s_dev, ws)
+        return dst
+
+    def check(self):
+        """Host sync: raise if the last batch held a malformed image descriptor or record."""
+        if self._status is not None:
+            v = int(self._status.item())
+            if v > 0:
+                raise RuntimeError("seq augment: image %d is misaligned, outside the declared maximum or carries a malformed record" % (v - 1))
+
+
 class TrainAugment:
     """aug = TrainAugment.from_config(config)
        images, targets, count = aug(groups)     # groups: [[(uint8 HWC RGB array, target [n,5] cls,cx,cy,w,h)] * 1..4]
@@ -67,9 +224,11 @@ class TrainAugment:
     With `seg_classes` (a config with a `seg:` section) a member is (image, target, seg_id), seg_id the uint8 [h,w] id
     map of the image, groups hold one image, and the call returns collate_fn's train-phase tuple
        images, targets, count, seg_maps = aug(groups)     # seg_maps [N,H/16,W/16,seg_classes] fp32 on `device`
-    ready for model(images, targets, seg_maps)."""
+    ready for model(images, targets, seg_maps).
+    With `seq` (a SeqAugment) the decoded images pass through the blur / sharpen / noise stage on the device first; the id
+    maps of a seg config do not (folder2lmdb.py:131).  Targets, count and the state of `rng` are those of seq=None."""
 
-    def __init__(self, train_img_size, mean, std, expand_scale, canvas=1000, device="cuda:0", rng=random, seg_classes=None):
+    def __init__(self, train_img_size, mean, std, expand_scale, canvas=1000, device="cuda:0", rng=random, seg_classes=None, seq=None):
         self.sizes = [tuple(int(v) for v in s) for s in train_img_size]
         self.mean = (ctypes.c_float * 3)(*[float(v) for v in mean])
         self.std = (ctypes.c_float * 3)(*[float(v) for v in std])
@@ -87,6 +246,7 @@ class TrainAugment:
                 raise ValueError("seg maps need square train_img_size entries, got %s" % (self.sizes,))
         self._seg_stage = None                      # pinned staging buffer of the id maps, grown on demand
         self._seg_status = None
+        self.seq = seq
 
     @classmethod
     def from_config(cls, cfg, **kw):
@@ -358,16 +518,21 @@ class TrainAugment:
         plan = self.plan(groups, size)
         stage, offsets = self.pack(groups)
         plan["items"]["offset"] = offsets
+        src = stage.to(self.device, non_blocking=True)
+        if self.seq is not None:
+            src = self.seq.run_device(src, plan["items"], self.seq.plan(len(plan["items"])))
         if self.seg_classes is None:
-            images = self.run_device(stage.to(self.device, non_blocking=True), plan)
+            images = self.run_device(src, plan)
             return images, plan["targets"], plan["count"]
         seg_stage, seg_offsets = self.pack_seg(groups)
-        images = self.run_device(stage.to(self.device, non_blocking=True), plan)
+        images = self.run_device(src, plan)
         seg_maps = self.run_device_seg(seg_stage.to(self.device, non_blocking=True), seg_offsets, plan, items_dev=self._keep[1], samples_dev=self._keep[2])
         return images, plan["targets"], plan["count"], seg_maps
 
     def check(self):
         """Host sync: raise if the last batch held an image or record outside the declared bounds."""
+        if self.seq is not None:
+            self.seq.check()
         if self._status is not None:
             v = int(self._status.item())
             if v > 0:

@@ -7,6 +7,9 @@ next to the Pillow CPU path (the reference's per-sample work: photometric ops, e
 bicubic tiles, the BILINEAR resize + normalise) in images/s per core on this host.  Prints one JSON line; `step_share`
 is the device time over a --step-ms training step.
 usage: python tools/bench_augment.py [--iters 20] [--step-ms 36] [--cpu-samples 16]
+       python tools/bench_augment.py --seq      # the blur / sharpen / noise stage (SeqAugment / mny_aug_seq_batch) on the same batch, at the
+                                                # reference's draw probabilities, next to mny_aug_batch in the same process (device events, 5 warm-up
+                                                # + 200 timed calls, three alternating repeats), plus the batch with every image given one op kind
 """
 import argparse
 import json
@@ -86,11 +89,53 @@ def pillow_per_core(groups, n):
     return imgs / (time.perf_counter() - t0)
 
 
+def timed(fn, warm=5, calls=200):
+    """Mean ms per call between two device events."""
+    for _ in range(warm):
+        fn()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(calls):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / calls
+
+
+def seq_leg(aug, plan, src):
+    seq = augment.SeqAugment(seed=0)
+    items = plan["items"]
+    rec = seq.plan(len(items))
+    px3 = 3 * items["h"].astype(np.int64) * items["w"]
+    moved = lambda r: int((2 * px3 * np.maximum(r["n_ops"], 1)).sum())          # every pass reads and writes the image once
+    out = aug.run_device(src, plan)
+    seq.run_device(src, items, rec)
+    seq.check()
+    aug.check()
+    t_seq, t_aug = [], []
+    for _ in range(3):
+        t_seq.append(timed(lambda: seq.run_device(src, items, rec)))
+        t_aug.append(timed(lambda: aug.run_device(src, plan, out=out)))
+    seq_ms, aug_ms = float(np.median(t_seq)), float(np.median(t_aug))
+    res = {"images": len(items), "seq_ms": round(seq_ms, 4), "seq_ms_repeats": [round(t, 4) for t in t_seq], "aug_batch_ms": round(aug_ms, 4),
+           "aug_batch_ms_repeats": [round(t, 4) for t in t_aug], "seq_over_aug": round(seq_ms / aug_ms, 4), "bytes_moved": moved(rec),
+           "GB_s": round(moved(rec) / seq_ms / 1e6, 1), "ops": {str(k): int((rec["n_ops"] == k).sum()) for k in (0, 1, 2)}}
+    kinds = {"copy": [], "gauss": [(augment.SEQ_GAUSS, 0.7)], "median3": [(augment.SEQ_MEDIAN, 3)], "median5": [(augment.SEQ_MEDIAN, 5)],
+             "sharpen": [(augment.SEQ_SHARPEN, 0.05, 1.0)], "noise": [(augment.SEQ_NOISE, 4.0, True, 12345)]}
+    for name, ops in kinds.items():                                             # which op costs what: the whole batch under one kind
+        r = augment.seq_records([ops] * len(items))
+        ms = timed(lambda: seq.run_device(src, items, r), calls=100)
+        res["all_" + name + "_ms"] = round(ms, 4)
+        res["all_" + name + "_GB_s"] = round(moved(r) / ms / 1e6, 1)
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--step-ms", type=float, default=36.0)
     ap.add_argument("--cpu-samples", type=int, default=16)
+    ap.add_argument("--seq", action="store_true", help="measure the blur / sharpen / noise stage next to mny_aug_batch and exit")
     a = ap.parse_args()
     groups = voc_groups(256)
     aug = augment.TrainAugment(SIZES, MEAN, STD, EXPAND, rng=random.Random(0))
@@ -98,6 +143,8 @@ def main():
     stage, offsets = aug.pack(groups)
     plan["items"]["offset"] = offsets
     src = stage.to("cuda:0")
+    if a.seq:
+        return seq_leg(aug, plan, src)
     out = aug.run_device(src, plan)
     aug.check()
     times = []
