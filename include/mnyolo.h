@@ -675,6 +675,107 @@ size_t mny_aug_seq_ws_bytes(int n_items, int64_t src_bytes, int max_in_h, int ma
 int mny_aug_seq_batch(const uint8_t* src, const mny_image_desc* desc, const mny_aug_seq_item* seq, int n_items,
                       int max_in_h, int max_in_w, uint8_t* dst, void* ws, void* stream);
 
+/* ---- baseline JPEG decode: host entropy stage, device pixel stage (csrc/jpeg_host.h, csrc/jpeg.hip) -----------
+ * The reference decodes with cv2.imdecode on the loader workers (folder2lmdb.py:94) from the raw file bytes its LMDB
+ * stores (:266).  Here the decode is cut where the work changes character: marker parsing and Huffman decoding stay
+ * on the host (serial, branchy), everything per pixel runs on the device, and what crosses the bus is the quantised
+ * coefficients as int16, 3 bytes per pixel at 4:2:0, as much as the RGB upload it replaces.  The pixel arithmetic is
+ * integer work and equals libjpeg's default decode (ISLOW inverse DCT, fancy upsampling) bit for bit for streams a real
+ * encoder wrote: Pillow with libjpeg-turbo is pinned by the tests; cv2.imdecode uses the same library defaults but is
+ * not installed, so that one is unpinned.  For hostile coefficients the claim is memory safety and determinism only:
+ * libjpeg's 64-bit intermediates and masked range table are not reproduced.
+ *
+ * Streams taken: SOF0, 8-bit samples, 8-bit quantisation tables; one component, or three components YCbCr (JFIF, an
+ * Adobe marker with transform 1, or neither) with luma sampling 1x1, 2x1 or 2x2 and chroma 1x1; one interleaved scan;
+ * Huffman tables from DHT; DRI / RSTn; FF 00 stuffing and fill bytes.  Sides up to 16383.  Every other stream gets one
+ * of the non-zero MNY_JPEG_* statuses below and no coefficients; a bad image never fails a call.
+ *
+ * mny_jpeg_probe (HOST): reads the headers up to SOS, never past data + len.  info->h, w and ncomp are filled whenever a
+ *   frame header was read (also for a progressive stream); the rest only with status 0: hs, vs = the luma sampling
+ *   factors (1, 1 for one component), bw[c] x bh[c] = the block grid of plane c, padded to whole MCUs, n_coef = 64 *
+ *   sum bw[c] * bh[c].  Returns MNY_EINVAL for a null pointer only.
+ * mny_jpeg_entropy_batch (HOST): for image i the coefficients go to coef + coef_off[i] (int16 elements; a multiple of 8
+ *   so that the device loads 16 bytes), at most coef_cap[i] of them (fewer than n_coef: MNY_JPEG_ECAPACITY, nothing
+ *   written).  Blocks are de-zigzagged to natural order (index 8 * row + column), the planes follow one another
+ *   (plane_off), within a plane the blocks are row-major over the padded grid.  Coefficients saturate to int16.  items[i]
+ *   is the record the device reads: the sizes, the planes, the three quantisation tables in natural order, the status,
+ *   and coef_off[i].  n_threads is clamped to 1..16; image i is decoded by thread i mod n_threads, so the output does
+ *   not depend on timing; nothing is allocated.  Nothing is read past data[i] + len[i] and nothing is written outside
+ *   coef[coef_off[i] .. + coef_cap[i]); a failed image may leave part of its slice written.
+ *
+ * mny_jpeg_pixels_batch (DEVICE): coef and items as the host stage wrote them, copied to the device; desc (DEVICE,
+ *   [n]): where each image goes in dst, offset a multiple of 16, h and w equal to the item's.  Two launches:
+ *   (a) every 8x8 block of every plane: v = coef * q, then the 1-D inverse DCT below on the columns, each output
+ *       (x + 1024) >> 11, then on the rows, each output (x + 131072) >> 18, sample = clamp(x + 128, 0, 255), into uint8
+ *       planes in ws (ws + 256 + coef_off + plane_off, bw * 8 bytes per row).  Every shift is arithmetic, every
+ *       intermediate 32-bit.  With 13-bit constants, on (v0..v7):
+ *         z1 = (v2 + v6) * 4433; t2 = z1 - v6 * 15137; t3 = z1 + v2 * 6270; t0 = (v0 + v4) << 13; t1 = (v0 - v4) << 13;
+ *         t10 = t0 + t3; t13 = t0 - t3; t11 = t1 + t2; t12 = t1 - t2;
+ *         a0..a3 = v7, v5, v3, v1; z1 = a0 + a3; z2 = a1 + a2; z3 = a0 + a2; z4 = a1 + a3; z5 = (z3 + z4) * 9633;
+ *         a0 *= 2446; a1 *= 16819; a2 *= 25172; a3 *= 12299; z1 *= -7373; z2 *= -20995; z3 = z3 * -16069 + z5;
+ *         z4 = z4 * -3196 + z5; a0 += z1 + z3; a1 += z2 + z4; a2 += z2 + z3; a3 += z1 + z4;
+ *         out = (t10 + a3, t11 + a2, t12 + a1, t13 + a0, t13 - a0, t12 - a1, t11 - a2, t10 - a3)
+ *   (b) upsample, convert, write interleaved RGB to dst + desc[i].offset.  A chroma plane is first cropped to cw =
+ *       ceil(w / 2) (2x1, 2x2) by ch = ceil(h / 2) (2x2) real samples; a neighbour beyond an edge is the edge sample.
+ *         2x1: out[2i] = (3 p[i] + p[i-1] + 1) >> 2, out[2i+1] = (3 p[i] + p[i+1] + 2) >> 2
+ *         2x2: output row 2j takes s[i] = 3 p[j][i] + p[j-1][i], row 2j+1 takes s[i] = 3 p[j][i] + p[j+1][i]; then
+ *              out[2i] = (3 s[i] + s[i-1] + 8) >> 4, out[2i+1] = (3 s[i] + s[i+1] + 7) >> 4
+ *         cw <= 2: libjpeg does not filter such a plane, out[y][x] = p[y >> 1][x >> 1] (2x2) or p[y][x >> 1] (2x1)
+ *       and the result is cropped to h x w.  With cb -= 128, cr -= 128: r = y + ((91881 cr + 32768) >> 16), g = y +
+ *       ((-22554 cb - 46802 cr + 32768) >> 16), b = y + ((116130 cb + 32768) >> 16), each clamped to 0..255.  One
+ *       component writes y three times.
+ *   The int32 at ws+0 receives 0, or 1 + the lowest index of an item that is not sound: a non-zero status; sizes,
+ *   sampling, block grids, plane offsets or n_coef that do not agree with each other; coef_off negative or not a multiple
+ *   of 8; desc offset negative or not a multiple of 16; desc h, w different from the item's or above max_h, max_w.  Such
+ *   an image is neither read nor written: its bytes in dst are left for the caller's fallback decoder to fill.  Nothing
+ *   outside an image's 3 * h * w bytes is touched.  n at most 4096.  coef and ws 16-byte aligned.
+ *   What the kernels canNOT check is an upper bound: the call carries neither the size of coef nor that of dst, so that
+ *   coef_off + n_coef <= coef_elems for every item (the same range, in bytes, is the item's planes in ws) and that
+ *   desc offset + 3 * h * w lies inside dst are the caller's responsibility, as the size of dst is for mny_aug_seq_batch.
+ *   Records that mny_jpeg_entropy_batch wrote satisfy the first whenever its coef_off / coef_cap slices lie inside coef.
+ *   ws: mny_jpeg_ws_bytes(n, coef_elems), coef_elems = the int16 count of the coef buffer (0 = bad arguments).
+ *   No host sync, no allocation, no atomics; deterministic launch to launch. */
+#define MNY_JPEG_OK 0
+#define MNY_JPEG_ETRUNCATED 1   /* the data ends inside the headers or before the last MCU */
+#define MNY_JPEG_ENOTJPEG 2     /* no SOI */
+#define MNY_JPEG_EPROGRESSIVE 3 /* SOF2 */
+#define MNY_JPEG_EEXTENDED 4    /* SOF1 */
+#define MNY_JPEG_EARITHMETIC 5  /* arithmetic, lossless or differential frames */
+#define MNY_JPEG_EPRECISION 6   /* 12-bit samples or 16-bit quantisation tables */
+#define MNY_JPEG_ECOLORSPACE 7  /* CMYK / YCCK, RGB by Adobe transform or component ids, 2 components */
+#define MNY_JPEG_ESAMPLING 8    /* 4:4:0 and every other sampling outside 1x1, 2x1, 2x2 */
+#define MNY_JPEG_EMULTISCAN 9   /* the first scan does not hold every component */
+#define MNY_JPEG_EHUFFMAN 10    /* a code that is not in the table, a run past coefficient 63, an overfull table */
+#define MNY_JPEG_EMARKER 11     /* an unexpected marker, or one that is missing (RSTn, a table, SOF before SOS) */
+#define MNY_JPEG_EHEADER 12     /* a segment that contradicts itself */
+#define MNY_JPEG_ETOOLARGE 13   /* a side above 16383 */
+#define MNY_JPEG_ECAPACITY 14   /* the caller's coefficient slice is too small, or a null / negative argument */
+typedef struct mny_jpeg_info {
+    int32_t status; /* MNY_JPEG_* */
+    int32_t h, w, ncomp;
+    int32_t hs, vs; /* luma sampling factors */
+    int32_t bw[3], bh[3];
+    int64_t n_coef;
+} mny_jpeg_info; /* 56 bytes */
+typedef struct mny_jpeg_item {
+    int32_t status;
+    int32_t h, w, ncomp;
+    int32_t hs, vs;
+    int32_t bw[3], bh[3];
+    int64_t coef_off;     /* int16 elements from coef to plane 0 */
+    int64_t n_coef;
+    int64_t plane_off[3]; /* int16 elements from plane 0 */
+    int32_t reserved0[2];
+    uint16_t q[3][64];    /* per component, natural order; byte 96 of the record, so a row of 8 is one 16-byte load */
+    int32_t reserved[8];
+} mny_jpeg_item; /* 512 bytes */
+int mny_jpeg_probe(const uint8_t* data, int64_t len, mny_jpeg_info* info);
+int mny_jpeg_entropy_batch(const uint8_t* const* data, const int64_t* len, int n, int16_t* coef,
+                           const int64_t* coef_off, const int64_t* coef_cap, mny_jpeg_item* items, int n_threads);
+size_t mny_jpeg_ws_bytes(int n, int64_t coef_elems);
+int mny_jpeg_pixels_batch(const int16_t* coef, const mny_jpeg_item* items, int n, uint8_t* dst,
+                          const mny_image_desc* desc, int max_h, int max_w, void* ws, void* stream);
+
 /* ---- bf16 STORAGE twins (BASELINE config 4: MobileNetV3-YOLO 512x512 bf16) -----------------
  * Every `mny_X_bf16` has the contract of `mny_X` above with ONE difference: the activation-sized tensors (the
  * `void*` parameters: raw conv outputs, materialised sums, gradients wrt activations) are bf16 in HBM.  Kernels

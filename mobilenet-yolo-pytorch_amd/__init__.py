@@ -5,3 +5,5 @@ from . import _lib  # noqa: F401
 from ._lib import MnyError  # noqa: F401
 from .model import yolo, HeadState  # noqa: F401
 from . import mbv3  # noqa: F401
+from . import jpeg  # noqa: F401
+from .jpeg import JpegDecoder  # noqa: F401

@@ -133,6 +133,10 @@ _SIGS = {
     "mny_aug_seg_batch": (c_int, [P, P, P, c_int, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P]),
     "mny_aug_seq_ws_bytes": (c_size_t, [c_int, c_int64, c_int, c_int]),
     "mny_aug_seq_batch": (c_int, [P, P, P, c_int, c_int, c_int, P, P, P]),
+    "mny_jpeg_probe": (c_int, [P, c_int64, P]),
+    "mny_jpeg_entropy_batch": (c_int, [P, P, c_int, P, P, P, P, c_int]),
+    "mny_jpeg_ws_bytes": (c_size_t, [c_int, c_int64]),
+    "mny_jpeg_pixels_batch": (c_int, [P, P, c_int, P, P, c_int, c_int, P, P]),
     "mny_eval_pack":(c_int, [P, c_int64, P, c_int64, P, P, P, P, P, P, P]),
 }
 # bf16-storage twins (activation tensors bf16, everything else as in the fp32 entry point): identical ctypes signature

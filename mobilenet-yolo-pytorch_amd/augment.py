@@ -25,7 +25,11 @@ stage is parity-unpinned against the third-party libraries, the arithmetic state
 no phase check); `SeqAugment.run_device` in front of `BatchPrep.run_device` reproduces that quirk for whoever wants it, it
 is not a default.
 
-Not covered (stays with the caller): JPEG decoding, the sampler, and the scale < 1 path of the area resize (a cropped
+With `decoder` (a jpeg.JpegDecoder) the members carry the encoded JPEG streams in place of the decoded arrays: the decoder
+fills the packed buffer on the device (host entropy decode, HIP pixels) and the plan is made from the decoded sizes; draws,
+targets and the state of `rng` are those of the array path.  Seg id maps are not JPEG and stay decoded by the caller.
+
+Not covered (stays with the caller): the sampler, and the scale < 1 path of the area resize (a cropped
 geometry smaller than the S/16 grid is refused).  No CPU fallback: without libmnyolo.so every call raises MnyError."""
 import ctypes
 import math
@@ -35,7 +39,7 @@ import numpy as np
 import torch
 
 from ._lib import call, query
-from .prep import DESC, BatchPrep
+from .prep import DESC, BatchPrep, all_encoded
 
 BRIGHTNESS, CONTRAST, SATURATION, HUE, GAMMA = range(5)      # MNY_AUG_*; image_augmentation.py:178-182 order
 
@@ -226,9 +230,11 @@ class TrainAugment:
        images, targets, count, seg_maps = aug(groups)     # seg_maps [N,H/16,W/16,seg_classes] fp32 on `device`
     ready for model(images, targets, seg_maps).
     With `seq` (a SeqAugment) the decoded images pass through the blur / sharpen / noise stage on the device first; the id
-    maps of a seg config do not (folder2lmdb.py:131).  Targets, count and the state of `rng` are those of seq=None."""
+    maps of a seg config do not (folder2lmdb.py:131).  Targets, count and the state of `rng` are those of seq=None.
+    With `decoder` (a jpeg.JpegDecoder) a member's first entry may be its encoded JPEG stream (bytes-like or a 1-D uint8
+    array); a batch holds streams or arrays, not both."""
 
-    def __init__(self, train_img_size, mean, std, expand_scale, canvas=1000, device="cuda:0", rng=random, seg_classes=None, seq=None):
+    def __init__(self, train_img_size, mean, std, expand_scale, canvas=1000, device="cuda:0", rng=random, seg_classes=None, seq=None, decoder=None):
         self.sizes = [tuple(int(v) for v in s) for s in train_img_size]
         self.mean = (ctypes.c_float * 3)(*[float(v) for v in mean])
         self.std = (ctypes.c_float * 3)(*[float(v) for v in std])
@@ -247,6 +253,7 @@ class TrainAugment:
         self._seg_stage = None                      # pinned staging buffer of the id maps, grown on demand
         self._seg_status = None
         self.seq = seq
+        self.decoder = decoder
 
     @classmethod
     def from_config(cls, cfg, **kw):
@@ -498,8 +505,9 @@ class TrainAugment:
                 if len(m) < 3:
                     raise ValueError("a seg config takes (image, target, seg_id) members")
                 a = m[2].numpy() if isinstance(m[2], torch.Tensor) else np.asarray(m[2])
-                if a.dtype != np.uint8 or a.shape != tuple(m[0].shape[:2]):
-                    raise ValueError("seg_id must be uint8 [h,w] of the image's size %s, got %s %s" % (tuple(m[0].shape[:2]), a.dtype, a.shape))
+                hw = tuple(int(v) for v in (m[0] if isinstance(m[0], tuple) else m[0].shape[:2]))
+                if a.dtype != np.uint8 or a.shape != hw:
+                    raise ValueError("seg_id must be uint8 [h,w] of the image's size %s, got %s %s" % (hw, a.dtype, a.shape))
                 arrs.append(a)
         offsets, off = np.zeros(len(arrs), np.int64), 0
         for i, a in enumerate(arrs):
@@ -515,10 +523,17 @@ class TrainAugment:
         return self._seg_stage[:off], offsets
 
     def __call__(self, groups, size=None):
-        plan = self.plan(groups, size)
-        stage, offsets = self.pack(groups)
-        plan["items"]["offset"] = offsets
-        src = stage.to(self.device, non_blocking=True)
+        if self.decoder is not None and all_encoded([m[0] for g in groups for m in g]):
+            src, desc, _, _ = self.decoder([m[0] for g in groups for m in g])
+            hw = iter((int(d["h"]), int(d["w"])) for d in desc)
+            groups = [[(next(hw),) + tuple(m[1:]) for m in g] for g in groups]   # plan() and pack_seg() need the sizes only
+            plan = self.plan(groups, size)
+            plan["items"]["offset"] = desc["offset"]
+        else:
+            plan = self.plan(groups, size)
+            stage, offsets = self.pack(groups)
+            plan["items"]["offset"] = offsets
+            src = stage.to(self.device, non_blocking=True)
         if self.seq is not None:
             src = self.seq.run_device(src, plan["items"], self.seq.plan(len(plan["items"])))
         if self.seg_classes is None:

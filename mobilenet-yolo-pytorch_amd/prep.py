@@ -1,8 +1,10 @@
 """Device-side batch input preparation — host mirror of the image half of the reference's
 `collate_fn` (folder2lmdb.py:223-256): one `random.choice(train_img_size)` per batch, every decoded image resized with
 Pillow's BILINEAR semantics, ToTensor, Normalize, stacked — here as ONE packed upload + `mny_prep_batch` (csrc/prep.hip),
-returning the NCHW fp32 batch on the GPU.  JPEG decoding, augmentation and the seg-map resize (cv2 INTER_AREA; cv2 is not
-available to pin it) stay with the caller.  No CPU fallback: without libmnyolo.so every call raises MnyError."""
+returning the NCHW fp32 batch on the GPU.  Augmentation and the seg-map resize (cv2 INTER_AREA; cv2 is not available to pin
+it) stay with the caller; so does JPEG decoding unless a `decoder=` (jpeg.JpegDecoder) is given, in which case the members are
+the encoded streams and the decoder's device buffer takes the place of the packed upload.  No CPU fallback: without
+libmnyolo.so every call raises MnyError."""
 import ctypes
 import random
 
@@ -14,12 +16,30 @@ from ._lib import call, query
 DESC = np.dtype([("offset", np.int64), ("h", np.int32), ("w", np.int32)])       # mny_image_desc
 
 
+def is_encoded(im):
+    """An encoded image (what the reference's LMDB yields): bytes-like, or a 1-D uint8 array."""
+    if isinstance(im, (bytes, bytearray, memoryview)):
+        return True
+    if isinstance(im, torch.Tensor):
+        return im.ndim == 1 and im.dtype == torch.uint8
+    return isinstance(im, np.ndarray) and im.ndim == 1 and im.dtype == np.uint8
+
+
+def all_encoded(members):
+    """True: every member is an encoded stream; False: none is.  A mixed batch raises."""
+    enc = [is_encoded(m) for m in members]
+    if any(enc) and not all(enc):
+        raise ValueError("a batch holds decoded [h,w,3] arrays or encoded streams, not both")
+    return bool(enc) and enc[0]
+
+
 class BatchPrep:
     """prep = BatchPrep(config["train_img_size"], config["normalize"]["mean"], config["normalize"]["std"])
        images = prep(list_of_uint8_hwc_arrays)            # -> [N,3,H,W] float32 on `device`, size drawn per batch
+    With `decoder=JpegDecoder()` the members may be encoded JPEG streams (bytes-like or 1-D uint8 arrays) instead.
     """
 
-    def __init__(self, train_img_size, mean, std, device="cuda:0", rng=None):
+    def __init__(self, train_img_size, mean, std, device="cuda:0", rng=None, decoder=None):
         self.sizes = [tuple(int(v) for v in s) for s in train_img_size]
         self.mean = (ctypes.c_float * 3)(*[float(v) for v in mean])
         self.std = (ctypes.c_float * 3)(*[float(v) for v in std])
@@ -27,6 +47,7 @@ class BatchPrep:
         self.rng = rng or random                    # the reference draws from the global `random` (folder2lmdb.py:227)
         self._stage = None                          # pinned staging buffer, grown on demand
         self._status = None
+        self.decoder = decoder                      # jpeg.JpegDecoder: takes encoded members
 
     def choose_size(self):
         return self.rng.choice(self.sizes)          # folder2lmdb.py:227
@@ -70,8 +91,11 @@ class BatchPrep:
         if len(images) == 0:
             raise ValueError("empty batch")
         size = size or self.choose_size()
-        stage, desc, mh, mw = self.pack(images)
-        src = stage.to(self.device, non_blocking=True)
+        if self.decoder is not None and all_encoded(images):
+            src, desc, mh, mw = self.decoder(images)
+        else:
+            stage, desc, mh, mw = self.pack(images)
+            src = stage.to(self.device, non_blocking=True)
         desc_dev = torch.from_numpy(desc.view(np.uint8).copy()).to(self.device, non_blocking=True)
         return self.run_device(src, desc_dev, len(images), mh, mw, size)
 
