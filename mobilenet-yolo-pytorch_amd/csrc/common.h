@@ -44,9 +44,10 @@ __device__ __forceinline__ float act_fwd(float z, int act) {
     return fminf(fmaxf(z, act_slope(act) * z), act_hi(act));
 }
 // derivative at pre-activation z (torch's subgradient choices: relu6 = hardtanh: 1 on the open interval (0,6);
-// leaky_relu: z > 0 ? 1 : slope)
+// leaky_relu: z > 0 ? 1 : slope).  h-swish': (2z + 3) / 6 as ONE fma, z / 3 + 1 / 2 — the form every fused kernel uses; it is the
+// correctly rounded fp64 value at z = 0 and beside it (tests/test_gpu_bn_glue.py), which (2z + 3) * (1 / 6) missed by an ulp
 __device__ __forceinline__ float act_bwd(float z, int act) {
-    if (act == MNY_ACT_HSWISH) return z <= -3.f ? 0.f : (z >= 3.f ? 1.f : (2.f * z + 3.f) * (1.f / 6.f));
+    if (act == MNY_ACT_HSWISH) return z <= -3.f ? 0.f : (z >= 3.f ? 1.f : fmaf(z, 1.f / 3.f, 0.5f));
     if (act == MNY_ACT_HSIGMOID) return (z > -3.f && z < 3.f) ? (1.f / 6.f) : 0.f;
     return (z > 0.f ? 1.f : act_slope(act)) * (z < act_hi(act) ? 1.f : 0.f);
 }

@@ -197,8 +197,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, 8))) v
                 const v2f z = __builtin_elementwise_fma(Y.v[j], sc.v[j], sh.v[j]);
                 v2f f;
                 if (am == 2) {
-                    f.x = z.x <= -3.f ? 0.f : (z.x >= 3.f ? 1.f : (2.f * z.x + 3.f) * (1.f / 6.f));
-                    f.y = z.y <= -3.f ? 0.f : (z.y >= 3.f ? 1.f : (2.f * z.y + 3.f) * (1.f / 6.f));
+                    f.x = z.x <= -3.f ? 0.f : (z.x >= 3.f ? 1.f : fmaf(z.x, 1.f / 3.f, 0.5f));
+                    f.y = z.y <= -3.f ? 0.f : (z.y >= 3.f ? 1.f : fmaf(z.y, 1.f / 3.f, 0.5f));
                 } else {
                     f.x = (z.x > 0.f ? 1.f : slope) * (z.x < hi ? 1.f : 0.f);
                     f.y = (z.y > 0.f ? 1.f : slope) * (z.y < hi ? 1.f : 0.f);
@@ -419,8 +419,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, 8))) v
                             const v2f z = __builtin_elementwise_fma(xr[jc].v[j], xsc.v[j], xsh.v[j]);
                             v2f f;
                             if (xf == 1) f = v2f{(z.x > 0.f ? 1.f : 0.f) * (z.x < 6.f ? 1.f : 0.f), (z.y > 0.f ? 1.f : 0.f) * (z.y < 6.f ? 1.f : 0.f)};
-                            else if (xf == 2) f = v2f{z.x <= -3.f ? 0.f : (z.x >= 3.f ? 1.f : (2.f * z.x + 3.f) * (1.f / 6.f)),
-                                                      z.y <= -3.f ? 0.f : (z.y >= 3.f ? 1.f : (2.f * z.y + 3.f) * (1.f / 6.f))};
+                            else if (xf == 2) f = v2f{z.x <= -3.f ? 0.f : (z.x >= 3.f ? 1.f : fmaf(z.x, 1.f / 3.f, 0.5f)),
+                                                      z.y <= -3.f ? 0.f : (z.y >= 3.f ? 1.f : fmaf(z.y, 1.f / 3.f, 0.5f))};
                             else f = v2f{z.x > 0.f ? 1.f : xslope, z.y > 0.f ? 1.f : xslope};
                             const v2f dz = gq * f;
                             rs1.v[j] += dz;

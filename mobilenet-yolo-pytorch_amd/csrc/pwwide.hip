@@ -199,7 +199,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                     float dact;
                     if (XF == 0) dact = (zz > 0.f ? 1.f : rslope) * (zz < rhi ? 1.f : 0.f);      // clamp family (torch's subgradient choices, act_bwd)
                     else {                                       // h-swish / h-sigmoid: selects, no per-element branch on the wave-uniform kind
-                        const float dsw = zz <= -3.f ? 0.f : (zz >= 3.f ? 1.f : (2.f * zz + 3.f) * (1.f / 6.f));
+                        const float dsw = zz <= -3.f ? 0.f : (zz >= 3.f ? 1.f : fmaf(zz, 1.f / 3.f, 0.5f));
                         const float dsg = (zz > -3.f && zz < 3.f) ? (1.f / 6.f) : 0.f;
                         dact = rhsig ? dsg : dsw;
                     }
