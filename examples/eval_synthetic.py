@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Caller-side counterpart of the reference's validation pass (train.py:test(), :333-424) on synthetic data, everything
 after JPEG decode on the GPU:  decoded uint8 photos -> BatchPrep (Resize/ToTensor/Normalize of collate_fn) ->
-model.eval() forward (network + decode + per-class NMS) -> Evaluator (VOC07 11-point mAP) -> adjust_confidence.
+model.eval() forward (network + decode + per-class NMS) -> Evaluator (VOC07 11-point mAP, COCO-style AP / AR) -> adjust_confidence.
 
     python examples/eval_synthetic.py [--images 256] [--batch 64] [--size 352]
 """
@@ -48,6 +48,9 @@ def main():
     print("%d images in %.2f s; %d ground-truth boxes, %d detections; mAP %.4f (random weights); next val_conf %.2f" % (
         a.images, dt, ev.gt_box, ev.pred_box, mAP, conf))
     assert len(aps) == 20 and 0.0 <= mAP <= 1.0
+    coco = ev.compute_coco(image_size=(a.size, a.size))                            # COCO protocol on the same detections, network input pixels
+    print("COCO  " + "  ".join("%s %.4f" % (k, v) for k, v in coco.items() if k != "per_class_AP"))
+    assert len(coco["per_class_AP"]) == 20 and all(v == -1 or 0.0 <= v <= 1.0 for k, v in coco.items() if k != "per_class_AP")
 
 
 if __name__ == "__main__":

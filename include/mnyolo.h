@@ -505,6 +505,55 @@ int mny_eval_pack(const float* rows, int64_t D, const float* targets, int64_t T,
                   float* det_labels, float* det_scores, float* true_boxes, float* true_labels,
                   float* true_diff, void* stream);
 
+/* ---- COCO-style detection metrics on the device (csrc/cocoeval.hip) ------------------------------------
+ * AP averaged over IoU thresholds, AP by object size, AR at detection caps: the arithmetic of
+ * pycocotools.cocoeval.COCOeval for iouType='bbox' on the packed layout of mny_map_eval.  The package is not
+ * available where this library is developed, so the entry is NOT pinned against it: the rules below (restated
+ * in numpy, float64, in tests/coco_ref.py) are the specification.
+ * Inputs: as mny_map_eval with true_crowd[T] (!= 0: crowd) in place of true_diff; image_sizes[n_images,2] =
+ * (w, h) in pixels, NULL = (1, 1).  Classes 1..n_classes-1; a label that is not an integer in that range is
+ * never evaluated.  Parameters are HOST arrays, copied into the launch: iou_thrs[n_iou <= 16],
+ * rec_thrs[n_rec <= 128], max_dets[n_maxdet <= 4] (positive, ascending), area_rngs[n_area <= 8][2] (lo, hi in
+ * pixels^2), stat_desc[S <= 32][4] = (is_recall, IoU index or -1 = all, area index, cap index).
+ * Geometry (fp64, no fused multiply-add): X1 = x1*W, Y1 = y1*H, X2 = x2*W, Y2 = y2*H, w = X2-X1, h = Y2-Y1,
+ *   area = w*h; iw = min(dX1+dw, gX1+gw) - max(dX1, gX1), IoU 0 if iw <= 0, ih alike; inter = iw*ih;
+ *   union = crowd(g) ? area(d) : (area(d) + area(g)) - inter; iou = inter / union.
+ * Per (image, class) with a detection: detections sorted by descending score (stable in stored order,
+ *   -0.0 == 0.0, NaN last) and cut to max_dets[-1].
+ * Per area range: a ground truth is ignored if it is a crowd or its area is < lo or > hi; ground truths are
+ *   visited not-ignored first, then ignored, each group in stored order.
+ * Per threshold t, each detection in score order: best = min(t, 1-1e-10), m = none; for each ground truth:
+ *   skip it if matched at this t and no crowd; stop if m is not ignored and this one is; skip it if
+ *   iou < best; else best = iou, m = this (among equal IoUs the later one wins).  A matched detection inherits
+ *   m's ignore flag and marks m matched; an unmatched one whose own area is outside the range is ignored.
+ * Accumulate per (class k, area a, cap c): the first max_dets[c] detections of every (image, class) list,
+ *   in image order, sorted by descending score (stable); npig = not-ignored ground truths of (k, a); with
+ *   npig == 0 the entries are -1.  Per threshold: tp = cumsum(matched & ~ignored), fp = cumsum(~matched &
+ *   ~ignored), rc = tp/npig, pr = tp/(fp+tp+2.220446049250313e-16); recall = rc[-1] (0 without detections);
+ *   pr becomes its running maximum from the right; precision[r] = pr[first i with rc[i] >= rec_thrs[r]], 0
+ *   if there is none.
+ * Outputs (device, fp64): precision[n_iou,n_rec,K,n_area,n_maxdet], recall[n_iou,K,n_area,n_maxdet] with
+ *   K = n_classes-1; stats[S]: the mean of the entries > -1 of the slice a stat_desc row names (precision
+ *   over recall thresholds and classes, or recall over classes), -1 if there are none; per_class_ap[K]: the
+ *   same over all thresholds at area range 0 and the last cap.  Optional (NULL to skip), in STORED detection
+ *   order: det_match[n_area,n_iou,D] = packed index of the matched ground truth, -1 unmatched, -2 not
+ *   evaluated (rank >= max_dets[-1] or label out of range); det_ignore[n_area,n_iou,D] = 0 / 1.
+ * Counts are exact and precision / recall are single fp64 divisions of them; the means are fixed-order sums.
+ * No host sync, no floating-point atomics, deterministic.  Limits: n_classes <= 255, n_images < 2^24,
+ * D, T <= 2^30, and the parameter counts above; beyond them MNY_EINVAL (mny_coco_ws_bytes returns 0) with a
+ * mny_last_error text.  The number of ground truths per (image, class) has no limit.
+ * ws: mny_coco_ws_bytes(...) bytes. */
+size_t mny_coco_ws_bytes(int64_t D, int64_t T, int n_images, int n_classes, int n_iou, int n_rec, int n_area,
+                         int n_maxdet);
+int mny_coco_eval(const float* det_boxes /*[D,4]*/, const float* det_labels, const float* det_scores,
+                  const int32_t* det_off /*[n_images+1]*/, const float* true_boxes /*[T,4]*/,
+                  const float* true_labels, const float* true_crowd, const int32_t* true_off,
+                  const float* image_sizes /*[n_images,2], NULL = (1,1)*/, int n_images, int64_t D, int64_t T,
+                  int n_classes, const double* iou_thrs, int n_iou, const double* rec_thrs, int n_rec,
+                  const int32_t* max_dets, int n_maxdet, const double* area_rngs, int n_area,
+                  const int32_t* stat_desc /*[S,4]*/, int S, double* precision, double* recall, double* stats,
+                  double* per_class_ap, int32_t* det_match, uint8_t* det_ignore, void* ws, void* stream);
+
 /* ---- segmentation head of the BDD100K config ------------------------------------------------
  * Replaces SegLoss.forward (models/seg_loss.py:51-80) and its autograd on the channels-last seg head
  * [N,h,w,C] (the reference permutes seg_maps [N,h,w,C] to NCHW instead, :54): n = N*h*w*C elements.

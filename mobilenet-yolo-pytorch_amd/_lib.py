@@ -121,6 +121,9 @@ _SIGS = {
     "mny_nms_prefix_offset": (c_size_t, [c_int, c_int, c_int]),
     "mny_map_ws_bytes": (c_size_t, [c_int64, c_int64]),
     "mny_map_eval": (c_int, [P, P, P, P, P, P, P, P, c_int, c_int64, c_int64, c_int, P, P, P, P, P, P, P]),
+    "mny_coco_ws_bytes": (c_size_t, [c_int64, c_int64, c_int, c_int, c_int, c_int, c_int, c_int]),
+    "mny_coco_eval": (c_int, [P, P, P, P, P, P, P, P, P, c_int, c_int64, c_int64, c_int, P, c_int, P, c_int, P, c_int, P, c_int, P, c_int,
+                              P, P, P, P, P, P, P, P]),
     "mny_seg_loss_ws_bytes": (c_size_t, [c_int64]),
     "mny_seg_loss": (c_int, [P, P, c_int64, P, P, P, P]),
     "mny_seg_sigmoid": (c_int, [P, c_int, c_int, c_int, P, P]),
