@@ -2,8 +2,11 @@
 """Caller-side counterpart of the reference's validation pass (train.py:test(), :333-424) on synthetic data, everything
 after JPEG decode on the GPU:  decoded uint8 photos -> BatchPrep (Resize/ToTensor/Normalize of collate_fn) ->
 model.eval() forward (network + decode + per-class NMS) -> Evaluator (VOC07 11-point mAP, COCO-style AP / AR) -> adjust_confidence.
+With --seg C the config gets a `seg:` section of C classes (the BDD100K config has 2: the drivable-area head) and the batched seg
+logits are scored against full-resolution id maps by segeval.SegEvaluator: per-class IoU, mIoU, pixel accuracy — no seg map is
+copied to the host except the reference's own seg_out of image 0.
 
-    python examples/eval_synthetic.py [--images 256] [--batch 64] [--size 352]
+    python examples/eval_synthetic.py [--images 256] [--batch 64] [--size 352] [--seg 2]
 """
 import argparse
 import os
@@ -17,6 +20,22 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from mobilenet_yolo_pytorch_amd import synthetic, yolo  # noqa: E402
 from mobilenet_yolo_pytorch_amd.evalmap import Evaluator, adjust_confidence  # noqa: E402
 from mobilenet_yolo_pytorch_amd.prep import BatchPrep  # noqa: E402
+from mobilenet_yolo_pytorch_amd.segeval import SegEvaluator  # noqa: E402
+
+
+def id_maps(sizes, n_classes, seed):
+    """Synthetic ground truth: uint8 id maps at the photos' sizes, one vertical band per class above a background sky, a strip of
+    ignored pixels (255) at the bottom."""
+    r = np.random.RandomState(seed)
+    out = []
+    for h, w in sizes:
+        m = np.zeros((h, w), np.uint8)
+        cuts = np.sort(r.randint(0, w, n_classes + 1))
+        for c in range(n_classes):
+            m[h // 2:, cuts[c]:cuts[c + 1]] = c + 1
+        m[h - 8:] = 255
+        out.append(m)
+    return out
 
 
 def main():
@@ -24,23 +43,31 @@ def main():
     ap.add_argument("--images", type=int, default=256)
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--size", type=int, default=352)
+    ap.add_argument("--seg", type=int, default=0, help="classes of a segmentation head (0: the VOC config, no head)")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
-    model = yolo(synthetic.VOC_CONFIG).to(dev).eval()
+    cfg = dict(synthetic.VOC_CONFIG, seg={"num_classes": a.seg}) if a.seg else synthetic.VOC_CONFIG
+    model = yolo(cfg).to(dev).eval()
     for hs in model.yolo_losses:
         hs.val_conf = 0.3
     classes_name = ["background"] + ["class%d" % i for i in range(1, 21)]          # train.py:57-58
     prep = BatchPrep([(a.size, a.size)], [0.485, 0.456, 0.406], [0.229, 0.224, 0.225], device=dev)
     ev = Evaluator(classes_name)
+    seg_ev = SegEvaluator(a.seg, device=dev) if a.seg else None
     r = np.random.RandomState(0)
     t0 = time.perf_counter()
     for b in range(0, a.images, a.batch):
         n = min(a.batch, a.images - b)
-        photos = synthetic.photos([(int(r.randint(300, 500)), int(r.randint(300, 500))) for _ in range(n)], seed=b)   # "decoded JPEGs"
+        sizes = [(int(r.randint(300, 500)), int(r.randint(300, 500))) for _ in range(n)]
+        photos = synthetic.photos(sizes, seed=b)                                   # "decoded JPEGs"
         targets = synthetic.targets(n, seed=b + 1, empty_every=8)
         images = prep(photos)                                                      # folder2lmdb.py:223-256 on the device
-        ev.add(model(images), targets)                                             # train.py:364-395
+        out = model(images)
+        if seg_ev is not None:
+            out = out[0]                                                           # (dets, seg_out of image 0): the reference's return
+            seg_ev.add(model.seg_logits(), id_maps(sizes, a.seg, seed=b + 2))      # all n seg outputs, at each label's own size
+        ev.add(out, targets)                                                       # train.py:364-395
     aps, mAP, tp, fp = ev.compute()                                                # train.py:421
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
@@ -51,6 +78,12 @@ def main():
     coco = ev.compute_coco(image_size=(a.size, a.size))                            # COCO protocol on the same detections, network input pixels
     print("COCO  " + "  ".join("%s %.4f" % (k, v) for k, v in coco.items() if k != "per_class_AP"))
     assert len(coco["per_class_AP"]) == 20 and all(v == -1 or 0.0 <= v <= 1.0 for k, v in coco.items() if k != "per_class_AP")
+    if seg_ev is not None:
+        seg = seg_ev.compute()                                                     # the one host sync of the seg leg
+        print("SEG   " + "  ".join("IoU[%s] %.4f" % kv for kv in seg["iou"].items())
+              + "  mIoU %.4f  mIoU(fg) %.4f  pixel acc %.4f  (%d pixels, %d ignored)" % (
+                  seg["miou"], seg["miou_fg"], seg["pixel_acc"], int(seg_ev.confusion.sum()), int(seg_ev.ignored.item())))
+        assert int(seg_ev.confusion.sum()) > 0 and 0.0 <= seg["pixel_acc"] <= 1.0
 
 
 if __name__ == "__main__":

@@ -567,6 +567,46 @@ int mny_seg_loss(const float* head, const float* seg_maps, int64_t n, float* out
 int mny_seg_sigmoid(const float* head /*[N,h,w,C], image 0 is read*/, int h, int w, int C, float* out,
                     void* stream);
 
+/* ---- segmentation evaluation on the device (csrc/segeval.hip) --------------------------------------------------
+ * Scores the seg head against full-resolution ground-truth id maps: the reference has no such step (its test()
+ * loader returns no seg labels, folder2lmdb.py:264-265); the prediction rule is the one of its only consumer of
+ * the seg output, inference.py:64-67,100-103 (each class map resized to the image with cv2.INTER_LINEAR, then
+ * > 0.5).  cv2 is restated, not linked: the arithmetic below IS the specification (tests/segeval_ref.py holds it
+ * in numpy, float64); it is half-pixel bilinear resizing without antialiasing, as
+ * torch.nn.functional.interpolate(mode="bilinear", align_corners=False) computes it.
+ * head: DEVICE fp32 [N,h,w,C], the raw seg logits, channels last.  Image i has its own size (H_i, W_i) =
+ * sizes[2i], sizes[2i+1]; sizes and the offsets are HOST arrays, read during the call (their entries travel in the
+ * kernel arguments, 96 images per launch).  1 <= C <= 16; h, w, H_i, W_i in 1..16384; w * C <= 6144.
+ *   p = 1 / (1 + expf(-x)) in fp32 (the sigmoid of mny_seg_sigmoid and mny_seg_loss).
+ *   Output row Y reads head rows clamp(y0, 0, h-1) and clamp(y0 + 1, 0, h-1) with weight ty, where, in integers,
+ *     ny = (2Y + 1) h - H_i, y0 = floor(ny / (2 H_i)), ry = ny - y0 * 2 H_i, and ty = (float)ry / (float)(2 H_i)
+ *     (both exact in fp32, one rounding); columns alike with w, W_i.
+ *   v = a (1 - ty) + b ty with a = p00 (1 - tx) + p01 tx, b = p10 (1 - tx) + p11 tx: every subtraction, product and
+ *     sum an fp32 operation of its own (no fused multiply-add).  At H_i = h, W_i = w every weight is 0 and v = p.
+ *   Predicted id: with m = max_c v_c, 0 (background) unless m > 0.5, else 1 + the lowest c with v_c == m; a NaN
+ *     never wins and never passes the threshold.
+ *   Ground truth: uint8 id maps, id c in 1..C = class c, 0 = background (folder2lmdb.py:140-141), an id above C
+ *     (e.g. 255) = ignored.
+ * mny_seg_confusion: labels / pred_out are DEVICE buffers, 16-byte aligned, image i at byte label_offsets[i] (a
+ *   multiple of 16) as H_i rows of W_i bytes with NO row padding.  conf[g][pred] += 1 in the int64 [(C+1),(C+1)]
+ *   DEVICE matrix and *ignored += 1 per ignored pixel: the call ADDS to what is there (integer sums: the result
+ *   does not depend on launch order).  pred_out (or NULL) receives the predicted id map in the labels' layout;
+ *   bytes between the images are not written.  labels may be NULL when only pred_out is wanted (conf and ignored
+ *   are then not touched).  Nothing is read past an image's H_i * W_i bytes.
+ * mny_seg_upsample: the interpolated probabilities v, image i as fp32 [C,H_i,W_i] at out + out_offsets[i] floats
+ *   (a multiple of 4; out 16-byte aligned): a batch of what inference.py:66-67 does per class.
+ * mny_seg_metrics: out (DEVICE fp64 [C+4]) = iou[0..C], miou, miou_fg, pixel_acc with
+ *   iou[k] = conf[k][k] / (row_k + col_k - conf[k][k]) (NaN at a zero denominator), miou the mean of the non-NaN
+ *   iou over 0..C, miou_fg over 1..C (sums in index order, NaN if there is none), pixel_acc = trace / sum.
+ * No host sync, no allocation, no workspace. */
+int mny_seg_confusion(const float* head /*[N,h,w,C]*/, int N, int h, int w, int C, const uint8_t* labels,
+                      const int64_t* label_offsets /*HOST [N]*/, const int32_t* label_sizes /*HOST [N,2] = (H, W)*/,
+                      int64_t* conf, int64_t* ignored, uint8_t* pred_out, void* stream);
+int mny_seg_upsample(const float* head /*[N,h,w,C]*/, int N, int h, int w, int C,
+                     const int32_t* sizes /*HOST [N,2] = (H, W)*/, const int64_t* out_offsets /*HOST [N]*/, float* out,
+                     void* stream);
+int mny_seg_metrics(const int64_t* conf /*[(C+1),(C+1)]*/, int C, double* out /*[C+4]*/, void* stream);
+
 /* ---- device-side batch input preparation ------------------------------------------------------
  * Replaces the image half of collate_fn (folder2lmdb.py:223-256): per image transforms.Resize(size, BILINEAR) on
  * the decoded PIL image, ToTensor, Normalize(mean, std), torch.stack — with the batch's one

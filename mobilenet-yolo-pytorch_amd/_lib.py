@@ -127,6 +127,9 @@ _SIGS = {
     "mny_seg_loss_ws_bytes": (c_size_t, [c_int64]),
     "mny_seg_loss": (c_int, [P, P, c_int64, P, P, P, P]),
     "mny_seg_sigmoid": (c_int, [P, c_int, c_int, c_int, P, P]),
+    "mny_seg_confusion": (c_int, [P, c_int, c_int, c_int, c_int, P, P, P, P, P, P, P]),
+    "mny_seg_upsample": (c_int, [P, c_int, c_int, c_int, c_int, P, P, P, P]),
+    "mny_seg_metrics": (c_int, [P, c_int, P, P]),
     "mny_prep_ws_bytes": (c_size_t, [c_int] * 5),
     "mny_prep_batch": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, P, P, P, P, P]),
     "mny_aug_ws_bytes": (c_size_t, [c_int] * 8),

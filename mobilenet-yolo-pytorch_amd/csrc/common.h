@@ -27,6 +27,10 @@ constexpr int kMaxParts = 1024;  // upper bound on stat/partial rows (4 blocks x
 
 __host__ __device__ inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// the reference's sigmoid (models/yolo_loss.py, seg_loss.py:19), one definition for every file that must agree on its bits:
+// accurate expf, one add, one correctly rounded divide
+__device__ __forceinline__ float sigmoid_ref(float x) { return 1.0f / (1.0f + expf(-x)); }
+
 // Branch-free activations.  relu6 / leaky(0.1) / relu / identity are all  min(max(z, slope*z), hi)  with
 // (slope, hi) = (0,6) / (0.1,inf) / (0,inf) / (1,inf); `act` is wave-uniform, so slope/hi live in SGPRs and the
 // per-element cost is v_mul + v_max + v_min (a per-element switch made the HBM-bound stencils VALU-bound).

@@ -29,8 +29,6 @@ struct LossWs {
     int nb1, nb2;
 };
 
-__device__ __forceinline__ float sigmoid_ref(float x) { return 1.0f / (1.0f + expf(-x)); }
-
 struct Box { float x1, y1, x2, y2; };
 
 // decode one cell; order of operations follows yolo_loss.py:89-92,243-247 (Q6, Q13)

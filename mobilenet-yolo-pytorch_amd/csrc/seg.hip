@@ -10,8 +10,6 @@ namespace {
 constexpr int kSegThreads = 256;
 constexpr int kSegMaxBlocks = 1024;
 
-__device__ __forceinline__ float sigmoid_ref(float x) { return 1.0f / (1.0f + expf(-x)); }   // seg_loss.py:19
-
 __global__ __launch_bounds__(kSegThreads) void seg_loss_kernel(const float* __restrict__ head, const float* __restrict__ truth, int64_t n, float gscale,
                                                                float* __restrict__ dhead, double* __restrict__ parts) {
     double sq = 0, so = 0, sn = 0, co = 0, cn = 0;

@@ -126,12 +126,13 @@ class yolo(nn.Module):
                             for i in range(2)]                                   # plain list: not in state_dict (mbv2_yolo.py:132)
         self.img_size = [config["img_w"], config["img_h"]]
         self._plans = {}
+        self._eval_plan = None                     # plan of the last eval forward (seg_logits)
         self._anchor = None
         self.grad_hook = None                      # DP: called as hook(plan) after gradients are complete
 
     def __getstate__(self):           # torch.save(model) (train.py:431): plans hold raw device pointers
         d = self.__dict__.copy()
-        d["_plans"], d["_anchor"], d["grad_hook"] = {}, None, None
+        d["_plans"], d["_anchor"], d["grad_hook"], d["_eval_plan"] = {}, None, None, None
         d.pop("dp_reducer", None)
         d.pop("_holders", None)
         return d
@@ -402,6 +403,7 @@ class yolo(nn.Module):
             plan = self._plan(N, H, W, False)
         with torch.no_grad():
             plan.forward_eval(x, [float(h.val_conf) for h in self.yolo_losses])
+            self._eval_plan = plan
             counts = plan.out_counts.tolist()                                   # the one host sync of the eval path
             if int(plan.nms_status.item()) != 0:
                 raise _lib.MnyError("NMS: a bucket of %d boxes exceeded the plan's per-image candidate bound" % int(plan.nms_status.item()))
@@ -411,3 +413,14 @@ class yolo(nn.Module):
         if plan.seg_head is not None:
             return dets, plan.seg_eval.cpu().numpy()                            # (output, seg_out) mbv2_yolo.py:161-164
         return dets
+
+    def seg_logits(self):
+        """The seg head's raw logits of the last eval forward, [N,h,w,C] fp32 on the device (all N images: the (dets, seg_out) return
+        keeps the reference's sigmoid of image 0 only).  A clone: the plan's buffer is overwritten by the next forward.  Feed it to
+        segeval.SegEvaluator.add / segeval.predict / segeval.upsample."""
+        if not self.has_seg:
+            raise _lib.MnyError("seg_logits: this config has no `seg:` section, the model has no segmentation head")
+        plan = getattr(self, "_eval_plan", None)
+        if plan is None or plan.seg_head is None:
+            raise _lib.MnyError("seg_logits: no eval forward has run yet (call model(images) without targets first)")
+        return plan.seg_head.to(torch.float32).clone()
