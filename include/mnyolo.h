@@ -1088,6 +1088,56 @@ int mny_gate_bwd3_bf16(const void* y3, const float* s3, const float* b3, const v
                        const float* mean3, const float* invstd3, void* dt, float* dw1_parts, float* red3, int64_t M, int C, int R,
                        void* stream);
 
+/* ---- Anchor fitting (csrc/anchors.hip): the anchors of config["yolo"]["anchors"] fitted to a label set on the device — k-means under
+ * the shape IoU, the fitness of many candidate sets in one launch, a mutation search, and a census of what mny_yolo_loss's target
+ * assignment will do with a set of anchors.  The reference has no counterpart: its anchors arrive ready-made in the config.  This text
+ * is the specification (restated in numpy by tests/anchor_ref.py); k-means and the search are not pinned against any third-party
+ * "autoanchor".  The census is pinned: it reproduces the positive count of mny_yolo_loss, and through the oracle get_target's.
+ *
+ * Shapes are wh[N,2] fp32 on the device, (w, h) in pixels, 16-byte aligned.
+ * Valid boxes.  A box is valid iff 2^-20 <= w <= 65536 and 2^-20 <= h <= 65536 (NaN fails the test).  Invalid boxes take part in
+ *   nothing and are counted in `skipped`.  Limits: 1 <= k <= 32, 1 <= N <= 2^22, 1 <= P <= 256; anything else is MNY_EINVAL with a
+ *   message and without a launch.  Centres, anchors and candidates are expected positive and finite (an IoU that is NaN never wins).
+ * Shape IoU.  inter = min(w,aw) * min(h,ah);  v = inter / ((w*h + aw*ah) - inter), every operation fp32 round-to-nearest in this
+ *   order, no contraction: find_jaccard_overlap (utils/iou.py:32-49) on [0,0,w,h] and [0,0,aw,ah].  best = the lowest index with the
+ *   largest v (strict >, starting from -inf at index 0).
+ * Fixed point.  Every sum that crosses lanes or workgroups is an integer, so no result depends on the launch order (no float atomics):
+ *   q(x) = llrint((double)x * 2^24) for shapes, qi(v) = llrint((double)v * 2^32) for IoUs (round to nearest even).
+ * k-means step.  (1) label every valid box with `best` against the current centres; (2) per centre S_w, S_h = int64 sums of q over
+ *   its boxes and n = their count; (3) a centre with n > 0 becomes (float)(((double)S / (double)n) * 2^-24) per coordinate; (4) a
+ *   centre with n == 0 keeps its value.  The run has converged at the first step that changes no bit of any centre; later steps are
+ *   the identity (the library skips them on a device flag).
+ *   mny_anchor_kmeans: centres[k,2] holds the initial centres and receives the result; max_iter (0..100000) steps are queued with no
+ *   host synchronisation, then a final pass writes labels[N] (int32 `best`, -1 for a skipped box) and, unless NULL, best_iou[N] (0
+ *   for a skipped box).  state = int64[4] on the device: {steps run up to and including the first that changed nothing (max_iter when
+ *   none did), converged 0/1, skipped, 0}.
+ * Fitness of P candidate sets cand[P,k,2] in one launch (mny_anchor_fitness): F[p] = sum of qi(best_v) over the valid boxes with
+ *   best_v > thr, R[p] = their count; thr is fp32 and thr = 0 gives the plain mean best IoU.  out = int64 [P][2] = (F, R); valid[1] =
+ *   the number of valid boxes.  mean best IoU = F * 2^-32 / valid, recall = R / valid.
+ * Evolution (mny_anchor_evolve): factors[G,P,k,2] fp32 on the device.  The parent starts as anchors_in[k,2].  In generation g candidate
+ *   0 is the parent verbatim and candidate p >= 1 is max(parent * factors[g,p], min_size) elementwise in fp32 (fmaxf); the candidate
+ *   with the largest F becomes the parent, ties to the lowest p, so F never decreases.  history = int64 [G][2] = (winning F, its p);
+ *   anchors_out[k,2] = the last parent (may alias anchors_in).  No host synchronisation inside.  How the factors are drawn is not part
+ *   of the ABI (anchors.draw_factors).  2^-20 <= min_size <= 65536.
+ * Census (mny_anchor_census): what mny_yolo_loss will do with these anchors.  targets[T,5] packed in the loss's layout (label, cx, cy,
+ *   w, h, relative to the image; 0 <= T <= 2^24), anchors_all[n,2] already divided by the image size (n <= 64), H <= 4 heads with
+ *   mask[H][A] (A <= 16) and grids[H] — these two are HOST arrays — and iou_thresh.  For every target, exactly as yolo_assign_kernel
+ *   (models/yolo_loss.py:127-146): best_n over all n anchors by the box IoU with the first maximum winning and a NaN counting as the
+ *   maximum; gi = (int)(cx * g), gj = (int)(cy * g) (truncation), the target is outside head h unless 0 <= gi, gj < g; otherwise
+ *   anchor slot a of head h is hit iff mask[h][a] == best_n or iou > iou_thresh.  out = int64 [n + H*A + 1 + H] =
+ *   best[n] (histogram of best_n over all targets) | pos[H][A] (hits: sum over a = the loss's count) | orphans (targets with no hit
+ *   in any head) | outside[H].
+ * ws: mny_anchor_ws_bytes(k, P) bytes, 16-byte aligned, for mny_anchor_kmeans (P = 1) and mny_anchor_evolve; the caller allocates
+ * everything and nothing is retained between calls. */
+size_t mny_anchor_ws_bytes(int k, int P);
+int mny_anchor_kmeans(const float* wh, int64_t N, float* centres, int k, int max_iter, int32_t* labels, float* best_iou, int64_t* state,
+                      void* ws, void* stream);
+int mny_anchor_fitness(const float* wh, int64_t N, const float* cand, int P, int k, float thr, int64_t* out, int64_t* valid, void* stream);
+int mny_anchor_evolve(const float* wh, int64_t N, const float* anchors_in, int k, const float* factors, int G, int P, float thr,
+                      float min_size, float* anchors_out, int64_t* history, void* ws, void* stream);
+int mny_anchor_census(const float* targets, int64_t T, const float* anchors_all, int n, const int32_t* mask, const int32_t* grids, int H,
+                      int A, float iou_thresh, int64_t* out, void* stream);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

@@ -6,4 +6,5 @@ from ._lib import MnyError  # noqa: F401
 from .model import yolo, HeadState  # noqa: F401
 from . import mbv3  # noqa: F401
 from . import jpeg  # noqa: F401
+from . import anchors  # noqa: F401
 from .jpeg import JpegDecoder  # noqa: F401

@@ -185,6 +185,12 @@ _SIGS["mny_transpose_bf16"] = _SIGS["mny_transpose"]
 _SIGS["mny_cvt_f32_bf16"] = (c_int, [P, P, c_int64, P])
 _SIGS["mny_cvt_batch_f32_bf16"] = (c_int, [P, P, c_int, P])
 _SIGS["mny_cvt_bf16_f32"] = (c_int, [P, P, c_int64, P])
+# anchor fitting (csrc/anchors.hip)
+_SIGS["mny_anchor_ws_bytes"] = (c_size_t, [c_int, c_int])
+_SIGS["mny_anchor_kmeans"] = (c_int, [P, c_int64, P, c_int, c_int, P, P, P, P, P])
+_SIGS["mny_anchor_fitness"] = (c_int, [P, c_int64, P, c_int, c_int, c_float, P, P, P])
+_SIGS["mny_anchor_evolve"] = (c_int, [P, c_int64, P, c_int, P, c_int, c_int, c_float, c_float, P, P, P, P])
+_SIGS["mny_anchor_census"] = (c_int, [P, c_int64, P, c_int, P, P, c_int, c_int, c_float, P, P])
 EXPORTS = tuple(_SIGS)
 
 _lib = None

@@ -12,6 +12,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "iou.h"      // Box, iou_ref: shared with anchors.hip
 
 namespace mny {
 
@@ -29,8 +30,6 @@ struct LossWs {
     int nb1, nb2;
 };
 
-struct Box { float x1, y1, x2, y2; };
-
 // decode one cell; order of operations follows yolo_loss.py:89-92,243-247 (Q6, Q13)
 __device__ __forceinline__ Box decode_box(float sx, float sy, float ew, float eh, int gx, int gy, float gf, float aw, float ah) {
     const float cx = (sx + (float)gx) / gf;
@@ -40,15 +39,6 @@ __device__ __forceinline__ Box decode_box(float sx, float sy, float ew, float eh
     b.x1 = cx - w / 2; b.y1 = cy - h / 2;
     b.x2 = w + b.x1; b.y2 = h + b.y1;
     return b;
-}
-
-__device__ __forceinline__ float iou_ref(const Box& a, const Box& b) {   // utils/iou.py:32-49 (a = set_1)
-    const float iw = fmaxf(fminf(a.x2, b.x2) - fmaxf(a.x1, b.x1), 0.f);
-    const float ih = fmaxf(fminf(a.y2, b.y2) - fmaxf(a.y1, b.y1), 0.f);
-    const float inter = iw * ih;
-    const float aa = (a.x2 - a.x1) * (a.y2 - a.y1);
-    const float ab = (b.x2 - b.x1) * (b.y2 - b.y1);
-    return inter / (aa + ab - inter);
 }
 
 // ---- pass 1: one thread per cell: decode, best IoU over the image's GTs, flags ------------------
