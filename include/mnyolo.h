@@ -764,6 +764,56 @@ size_t mny_aug_seq_ws_bytes(int n_items, int64_t src_bytes, int max_in_h, int ma
 int mny_aug_seq_batch(const uint8_t* src, const mny_image_desc* desc, const mny_aug_seq_item* seq, int n_items,
                       int max_in_h, int max_in_w, uint8_t* dst, void* ws, void* stream);
 
+/* ---- random perspective: rotation, scale, shear, translation, perspective (csrc/augwarp.hip) -------------------
+ * The geometric warp every YOLOv5-family trainer runs on every sample (random_perspective).  The reference has no
+ * counterpart: its geometry is axis-aligned (expand, crop, flip, Mosaic tiles).  The host draws and inverts one 3x3
+ * matrix per image (augment.py RandomPerspective.plan) and transforms the boxes; the device does the per-pixel gather,
+ * uint8 -> uint8, the output the size of the input, bit for bit what Pillow's Image.transform(size, PERSPECTIVE, c,
+ * BILINEAR or NEAREST, fillcolor) writes (tests/warp_ref.py restates it in numpy and is pinned to Pillow).
+ * Coordinates are Pillow's continuous ones: pixel (i, j) covers [i, i+1) x [j, j+1), its centre is (i+0.5, j+0.5);
+ * boxes use the same (cx * w etc.).  Everything below is fp64 without FMA contraction.
+ * c[0..7]: the INVERSE map, output -> source, normalised so that the ninth coefficient is 1.  For output pixel (x, y):
+ *   xi = x + 0.5, yi = y + 0.5; den = c6*xi + c7*yi + 1; xin = (c0*xi + c1*yi + c2) / den; yin = (c3*xi + c4*yi + c5) / den
+ *   (sums left to right).  With c6 == c7 == 0 den is exactly 1 and the division is skipped: the same bits.  den <= 0 or a
+ *   non-finite xin / yin writes the fill (Pillow defines neither case).
+ * channels 3, RGB, BILINEAR (bilinear_filter32RGB): xin < 0 || xin >= w || yin < 0 || yin >= h writes the fill; otherwise
+ *   xs = xin - 0.5, ys = yin - 0.5, X = floor(xs), Y = floor(ys), dx = xs - X, dy = ys - Y; x0 = clamp(X, 0, w-1), x1 =
+ *   clamp(X+1, 0, w-1), row y0 = clamp(Y, 0, h-1); per channel v1 = p[y0][x0] + (p[y0][x1] - p[y0][x0]) * dx; v2 the same
+ *   on row Y+1 if 0 <= Y+1 < h, else v2 = v1; v = v1 + (v2 - v1) * dy; out = (uint8)v, truncated.
+ * channels 1, NEAREST (id maps; nearest_filter8): the same four comparisons in fp64, before any conversion to int, write
+ *   the fill; otherwise out = p[(int)yin][(int)xin].
+ * fill: (127, 127, 127) for images (expand_od's filler), fill[0] = 0 for id maps (background, as expand_od's border).
+ * Host side (numpy fp64): the forward matrix is YOLOv5's composition M = T . S . R . P . C: C moves (w/2, h/2) to the
+ *   origin; P[2,0] = px, P[2,1] = py; R = [[s cos a, s sin a, 0], [-s sin a, s cos a, 0], [0, 0, 1]]; S[0,1] = tan(shx),
+ *   S[1,0] = tan(shy); T[0,2] = tx*w, T[1,2] = ty*h.  c = inv(M) / inv(M)[2,2], first eight entries (c6 = c7 = 0 exactly
+ *   when M[2,0] = M[2,1] = 0: the inverse of an affine map is affine, whatever the solver rounds).  M == identity exactly
+ *   marks the item `identity`: its image is copied byte for byte and its targets are left untouched.  Otherwise each box
+ *   goes to pixel corners, the four corners go through M with the perspective divide, the new box is their min / max
+ *   clipped to [0,w] x [0,h], and it is kept iff its new width > 2 px, its new height > 2 px, max(w'/h', h'/w') < 100 and
+ *   area' / (area * |det M[:2,:2]| + 1e-16) > 0.1; back to (cls, cx, cy, w, h) normalised, float32.  The forward
+ *   denominator M[2].(x, y, 1) must be positive at the four source corners.
+ * src: the packed upload of mny_aug_seq_batch: uint8 images, HWC, in one DEVICE buffer; desc (DEVICE, [n_items]): offset
+ * (a multiple of 4) and size of each, channels * h * w bytes; warp (DEVICE, [n_items]): one record per image.  dst is
+ * laid out like src (dst != src; src, dst and ws 4-byte aligned): after the call it holds EVERY image, an identity item
+ * copied byte for byte; bytes between and after the images are not written.  Nothing is read past an image's channels *
+ * h * w bytes.  max_in_h / max_in_w: the caller's bounds on the image sizes (at most 16383); n_items at most 4096.
+ * The int32 at ws+0 receives 0, or 1 + the lowest index of an item that is outside the bounds, misaligned or carries a
+ * non-finite coefficient.  Such an image is written as zeros (an item with a negative offset or a side outside 1..16383
+ * names no bytes and is only reported); nothing outside its bytes is touched.  That offset + channels * h * w lies inside
+ * src and dst is the caller's responsibility, as for mny_aug_seq_batch.
+ * ws: mny_aug_warp_ws_bytes() (0 = bad arguments).  One launch, no host sync, no allocation, no atomics; deterministic
+ * launch to launch. */
+typedef struct mny_aug_warp_item {
+    double c[8];      /* the inverse map, output -> source */
+    int32_t identity; /* non-zero: copy the image */
+    uint8_t fill[3];
+    uint8_t reserved;
+} mny_aug_warp_item; /* 72 bytes */
+size_t mny_aug_warp_ws_bytes(int n_items, int channels, int max_in_h, int max_in_w);
+int mny_aug_warp_batch(const uint8_t* src, const mny_image_desc* desc, const mny_aug_warp_item* warp, int n_items,
+                       int channels /* 3: RGB bilinear, 1: id map nearest */, int max_in_h, int max_in_w,
+                       uint8_t* dst, void* ws, void* stream);
+
 /* ---- baseline JPEG decode: host entropy stage, device pixel stage (csrc/jpeg_host.h, csrc/jpeg.hip) -----------
  * The reference decodes with cv2.imdecode on the loader workers (folder2lmdb.py:94) from the raw file bytes its LMDB
  * stores (:266).  Here the decode is cut where the work changes character: marker parsing and Huffman decoding stay

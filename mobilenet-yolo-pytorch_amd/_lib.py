@@ -139,6 +139,8 @@ _SIGS = {
     "mny_aug_seg_batch": (c_int, [P, P, P, c_int, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P]),
     "mny_aug_seq_ws_bytes": (c_size_t, [c_int, c_int64, c_int, c_int]),
     "mny_aug_seq_batch": (c_int, [P, P, P, c_int, c_int, c_int, P, P, P]),
+    "mny_aug_warp_ws_bytes": (c_size_t, [c_int] * 4),
+    "mny_aug_warp_batch": (c_int, [P, P, P, c_int, c_int, c_int, c_int, P, P, P]),
     "mny_jpeg_probe": (c_int, [P, c_int64, P]),
     "mny_jpeg_entropy_batch": (c_int, [P, P, c_int, P, P, P, P, c_int]),
     "mny_jpeg_ws_bytes": (c_size_t, [c_int, c_int64]),

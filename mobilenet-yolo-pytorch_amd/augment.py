@@ -25,6 +25,13 @@ stage is parity-unpinned against the third-party libraries, the arithmetic state
 no phase check); `SeqAugment.run_device` in front of `BatchPrep.run_device` reproduces that quirk for whoever wants it, it
 is not a default.
 
+`RandomPerspective` is a stage the reference does not have: YOLOv5's random_perspective (rotation, scale jitter, shear,
+translation, perspective).  `TrainAugment(..., warp=RandomPerspective(seed))` runs it after `seq` and before `mny_aug_batch`:
+`mny_aug_warp_batch` (csrc/augwarp.hip) gathers every decoded image through its inverse map, uint8 -> uint8 at source
+resolution, and the targets go through the forward matrix before `_member` sees them; the id maps of a seg config take the
+same coefficients.  Its draws come from a numpy Generator of its own.  The pixels equal Pillow's Image.transform(PERSPECTIVE)
+byte for byte (tests/warp_ref.py, pinned in tests/test_warp_ref_cpu.py).
+
 With `decoder` (a jpeg.JpegDecoder) the members carry the encoded JPEG streams in place of the decoded arrays: the decoder
 fills the packed buffer on the device (host entropy decode, HIP pixels) and the plan is made from the decoded sizes; draws,
 targets and the state of `rng` are those of the array path.  Seg id maps are not JPEG and stay decoded by the caller.
@@ -55,6 +62,8 @@ SEQ = np.dtype([("n_ops", np.int32), ("op", np.int32, 2), ("taps", np.float32, 5
                 ("sharpen_s", np.float32), ("noise_scale", np.float32), ("noise_per_channel", np.int32), ("noise_key", np.uint32, 2),
                 ("reserved", np.int32)])                                                          # mny_aug_seq_item
 assert SEQ.itemsize == 64
+WARP = np.dtype([("c", np.float64, 8), ("identity", np.int32), ("fill", np.uint8, 3), ("reserved", np.uint8)])   # mny_aug_warp_item
+assert WARP.itemsize == 72
 SEQ_SIGMA_MIN = 1e-3                                          # imgaug GaussianBlur: a sigma below this is the identity
 
 
@@ -221,6 +230,190 @@ class SeqAugment:
                 raise RuntimeError("seq augment: image %d is misaligned, outside the declared maximum or carries a malformed record" % (v - 1))
 
 
+def warp_matrix(h, w, degrees=0.0, scale=1.0, shear_x=0.0, shear_y=0.0, tx=0.5, ty=0.5, px=0.0, py=0.0):
+    """YOLOv5's random_perspective composition M = T . S . R . P . C (fp64), forward: source -> output.  Angles in degrees, tx / ty
+    the fractions of the width / height at which the centre lands (0.5 = stays)."""
+    C, P, R, S, T = (np.eye(3) for _ in range(5))
+    C[0, 2], C[1, 2] = -w / 2, -h / 2
+    P[2, 0], P[2, 1] = px, py
+    a = math.radians(degrees)
+    R[0, 0], R[0, 1], R[1, 0], R[1, 1] = scale * math.cos(a), scale * math.sin(a), -scale * math.sin(a), scale * math.cos(a)
+    S[0, 1], S[1, 0] = math.tan(math.radians(shear_x)), math.tan(math.radians(shear_y))
+    T[0, 2], T[1, 2] = tx * w, ty * h
+    return T @ S @ R @ P @ C
+
+
+def warp_coeffs(M):
+    """Forward 3x3 -> the eight coefficients of the inverse map, output -> source, the ninth normalised to 1 (what Pillow's
+    Image.transform(..., PERSPECTIVE, c) takes).  ValueError for a matrix that is not finite or not invertible."""
+    M = np.asarray(M, np.float64)
+    if M.shape != (3, 3) or not np.isfinite(M).all():
+        raise ValueError("a warp matrix must be a finite 3x3, got %r" % (M,))
+    if np.linalg.det(M) == 0:
+        raise ValueError("the warp matrix is singular: %r" % (M,))
+    inv = np.linalg.inv(M)
+    with np.errstate(all="ignore"):
+        c = (inv / inv[2, 2]).reshape(9)[:8]
+    if M[2, 0] == 0 and M[2, 1] == 0:
+        c[6] = c[7] = 0.0                                         # the inverse of an affine map is affine, whatever the solver's rounding
+    if not np.isfinite(c).all():
+        raise ValueError("the inverse of the warp matrix cannot be normalised (its last entry is %r): %r" % (inv[2, 2], M))
+    return c
+
+
+class RandomPerspective:
+    """warp = RandomPerspective(seed)               # YOLOv5's random_perspective, defaults of hyp.scratch-low
+       plan = warp.plan([(h, w), ...])              # host: WARP records, forward matrices, identity flags
+       dst = warp.run_device(src, desc, plan, channels=3)       # src: the packed uint8 upload; dst: the same layout
+       target = warp.boxes(target, plan["matrices"][i], h, w)   # host: the [n,5] cls,cx,cy,w,h rows of image i
+    or TrainAugment(..., warp=warp), which runs it after `seq` and before mny_aug_batch, on the id maps of a seg config too.
+    The reference has no such stage; the arithmetic in include/mnyolo.h is the specification and equals Pillow's
+    Image.transform(PERSPECTIVE) byte for byte (BILINEAR, fill 127 for images; NEAREST, fill 0 for id maps).
+    The draws come from a numpy Generator owned by the instance, never from Python's `random`.  Each draw is a vector over the
+    batch, drawn whether used or not, in this order: (1) gate < p; (2) a ~ U(-degrees, degrees); (3) s ~ U(1 - scale, 1 + scale);
+    (4) shx, (5) shy ~ U(-shear, shear), degrees; (6) tx, (7) ty ~ U(0.5 - translate, 0.5 + translate); (8) px, (9) py ~
+    U(-perspective, perspective).  The draws are a function of the seed and the batch size alone.  A gated-off image, and one
+    whose matrix equals the identity exactly, is an identity item: its bytes are copied and its targets left alone."""
+    FILL = (127, 127, 127)                                        # expand_od's filler
+
+    def __init__(self, seed=None, degrees=0.0, translate=0.1, scale=0.5, shear=0.0, perspective=0.0, p=1.0, device="cuda:0"):
+        self.gen = np.random.Generator(np.random.PCG64(seed))
+        self.degrees, self.translate, self.scale = float(degrees), float(translate), float(scale)
+        self.shear, self.perspective, self.p = float(shear), float(perspective), float(p)
+        self.device = torch.device(device)
+        self._fixed = None
+        self._status = {}
+        self._keep = {}
+
+    @classmethod
+    def fixed(cls, matrices, device="cuda:0"):
+        """Explicit forward 3x3 matrices (source -> output), one per image, in place of the draws.  A matrix that is not finite or
+        not invertible raises ValueError here; the denominator at the image's corners is checked by plan(), which knows the sizes."""
+        self = cls(0, device=device)
+        ms = np.array([np.asarray(m, np.float64) for m in matrices], np.float64).reshape(-1, 3, 3)
+        for i, m in enumerate(ms):
+            try:
+                warp_coeffs(m)
+            except ValueError as e:
+                raise ValueError("image %d: %s" % (i, e)) from None
+        self._fixed = ms
+        return self
+
+    def draw(self, n_images):
+        """The raw draws of one batch, in the documented order (host only)."""
+        g, n = self.gen, int(n_images)
+        d = dict(gate=g.random(n) < self.p)
+        d["a"] = g.uniform(-self.degrees, self.degrees, n)
+        d["s"] = g.uniform(1 - self.scale, 1 + self.scale, n)
+        d["shx"] = g.uniform(-self.shear, self.shear, n)
+        d["shy"] = g.uniform(-self.shear, self.shear, n)
+        d["tx"] = g.uniform(0.5 - self.translate, 0.5 + self.translate, n)
+        d["ty"] = g.uniform(0.5 - self.translate, 0.5 + self.translate, n)
+        d["px"] = g.uniform(-self.perspective, self.perspective, n)
+        d["py"] = g.uniform(-self.perspective, self.perspective, n)
+        return d
+
+    @staticmethod
+    def matrices(d, sizes):
+        """draw() and the (h, w) of every image -> forward matrices [n,3,3]; a gated-off image gets the identity."""
+        out = np.tile(np.eye(3), (len(sizes), 1, 1))
+        for i, (h, w) in enumerate(sizes):
+            if d["gate"][i]:
+                out[i] = warp_matrix(h, w, d["a"][i], d["s"][i], d["shx"][i], d["shy"][i], d["tx"][i], d["ty"][i], d["px"][i], d["py"][i])
+        return out
+
+    def plan(self, sizes):
+        """Host only.  sizes: the (h, w) of each of the batch's decoded images -> dict(records WARP array, matrices [n,3,3] forward,
+        identity bool [n]).  ValueError naming the image whose forward denominator is not positive at its four corners."""
+        sizes = [(int(h), int(w)) for h, w in sizes]
+        if self._fixed is not None:
+            if len(self._fixed) != len(sizes):
+                raise ValueError("fixed matrices describe %d images, the batch holds %d" % (len(self._fixed), len(sizes)))
+            ms = self._fixed.copy()
+        else:
+            ms = self.matrices(self.draw(len(sizes)), sizes)
+        rec = np.zeros(len(sizes), WARP)
+        rec["fill"] = self.FILL
+        ident = np.zeros(len(sizes), bool)
+        for i, ((h, w), m) in enumerate(zip(sizes, ms)):
+            ident[i] = bool(np.array_equal(m, np.eye(3)))
+            if ident[i]:
+                rec["c"][i] = (1, 0, 0, 0, 1, 0, 0, 0)
+                continue
+            den = [m[2, 0] * x + m[2, 1] * y + m[2, 2] for x, y in ((0, 0), (w, 0), (0, h), (w, h))]
+            if not min(den) > 0:
+                raise ValueError("image %d: the warp's denominator is not positive at every corner of the %dx%d image (%s); the "
+                                 "perspective terms are too large for this size" % (i, h, w, ", ".join("%g" % v for v in den)))
+            try:
+                rec["c"][i] = warp_coeffs(m)
+            except ValueError as e:
+                raise ValueError("image %d: %s" % (i, e)) from None
+        rec["identity"] = ident
+        return dict(records=rec, matrices=ms, identity=ident)
+
+    @staticmethod
+    def boxes(target, M, h, w):
+        """[n,5] cls,cx,cy,w,h (normalised) of an image of size (h, w) under the forward matrix M -> float32 [k,5]: the corners go
+        through M, the new box is their min / max clipped to the image; kept iff wider and higher than 2 px, aspect under 100 and
+        more than 0.1 of the area the map gives the whole box."""
+        t = np.asarray(target, np.float64).reshape(-1, 5)
+        M = np.asarray(M, np.float64)
+        x1, y1 = (t[:, 1] - t[:, 3] / 2) * w, (t[:, 2] - t[:, 4] / 2) * h
+        x2, y2 = (t[:, 1] + t[:, 3] / 2) * w, (t[:, 2] + t[:, 4] / 2) * h
+        xs, ys = np.stack([x1, x2, x1, x2], 1), np.stack([y1, y2, y2, y1], 1)
+        with np.errstate(all="ignore"):
+            den = M[2, 0] * xs + M[2, 1] * ys + M[2, 2]
+            X = (M[0, 0] * xs + M[0, 1] * ys + M[0, 2]) / den
+            Y = (M[1, 0] * xs + M[1, 1] * ys + M[1, 2]) / den
+            nx1, nx2 = np.clip(X.min(1), 0, w), np.clip(X.max(1), 0, w)
+            ny1, ny2 = np.clip(Y.min(1), 0, h), np.clip(Y.max(1), 0, h)
+            nw, nh = nx2 - nx1, ny2 - ny1
+            area = (x2 - x1) * (y2 - y1)
+            det = abs(M[0, 0] * M[1, 1] - M[0, 1] * M[1, 0])
+            keep = (nw > 2) & (nh > 2) & (np.maximum(nw / nh, nh / nw) < 100) & (nw * nh / (area * det + 1e-16) > 0.1)
+        out = np.stack([t[:, 0], (nx1 + nx2) / 2 / w, (ny1 + ny2) / 2 / h, nw / w, nh / h], 1)
+        return out[keep].astype(np.float32)
+
+    def run_device(self, src, desc_or_items, plan, channels=3):
+        """src: the packed uint8 images (channels 3, BILINEAR, fill 127) or id maps (channels 1, NEAREST, fill 0) on the device;
+        desc_or_items: their DESC array (prep.py) or TrainAugment's ITEM array with the offsets set; plan: plan(sizes) or its
+        records.  -> dst, laid out like src, every image in it."""
+        rec = plan["records"] if isinstance(plan, dict) else plan
+        n = len(desc_or_items)
+        if channels not in (1, 3):
+            raise ValueError("channels must be 3 (RGB images) or 1 (id maps), got %r" % (channels,))
+        if not isinstance(rec, np.ndarray) or rec.dtype != WARP or len(rec) != n:
+            raise ValueError("the plan must hold one WARP record per image")
+        if channels == 1:
+            rec = rec.copy()
+            rec["fill"] = 0                                     # background
+        desc = np.zeros(n, DESC)
+        for f in ("offset", "h", "w"):
+            desc[f] = desc_or_items[f]
+        max_h, max_w = int(desc["h"].max()), int(desc["w"].max())
+        size = query("mny_aug_warp_ws_bytes", n, channels, max_h, max_w)
+        if size == 0:
+            raise ValueError("mny_aug_warp_ws_bytes refused n=%d channels=%d max %dx%d" % (n, channels, max_h, max_w))
+        dev = src.device                                       # the stage runs where the upload is
+        ws = torch.empty(size, device=dev, dtype=torch.uint8)
+        dst = torch.empty_like(src)
+        d_dev = torch.from_numpy(desc.view(np.uint8).copy()).to(dev, non_blocking=True)
+        w_dev = torch.from_numpy(np.ascontiguousarray(rec).view(np.uint8).copy()).to(dev, non_blocking=True)
+        p = lambda t: ctypes.c_void_p(t.data_ptr())
+        call("mny_aug_warp_batch", p(src), p(d_dev), p(w_dev), n, channels, max_h, max_w, p(dst), p(ws), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+        self._status[channels] = ws[:4].view(torch.int32)
+        self._keep[channels] = (src, d_dev, w_dev, ws)
+        return dst
+
+    def check(self):
+        """Host sync: raise if the last batch (its images or its id maps) held a malformed descriptor or record."""
+        for channels, st in sorted(self._status.items(), reverse=True):
+            v = int(st.item())
+            if v > 0:
+                raise RuntimeError("warp augment: %s %d is misaligned, outside the declared maximum or carries a non-finite coefficient"
+                                   % ("image" if channels == 3 else "seg map", v - 1))
+
+
 class TrainAugment:
     """aug = TrainAugment.from_config(config)
        images, targets, count = aug(groups)     # groups: [[(uint8 HWC RGB array, target [n,5] cls,cx,cy,w,h)] * 1..4]
@@ -232,9 +425,14 @@ class TrainAugment:
     With `seq` (a SeqAugment) the decoded images pass through the blur / sharpen / noise stage on the device first; the id
     maps of a seg config do not (folder2lmdb.py:131).  Targets, count and the state of `rng` are those of seq=None.
     With `decoder` (a jpeg.JpegDecoder) a member's first entry may be its encoded JPEG stream (bytes-like or a 1-D uint8
-    array); a batch holds streams or arrays, not both."""
+    array); a batch holds streams or arrays, not both.
+    With `warp` (a RandomPerspective) every decoded image is rotated / scaled / sheared / translated / projected at source
+    resolution after `seq`, its target goes through the same matrix before the reference's chain sees it, and the id map of a
+    seg config takes the image's coefficients (NEAREST, border 0).  `rng` is not touched: its draws are those of warp=None on
+    the transformed targets, and an all-identity warp changes nothing."""
 
-    def __init__(self, train_img_size, mean, std, expand_scale, canvas=1000, device="cuda:0", rng=random, seg_classes=None, seq=None, decoder=None):
+    def __init__(self, train_img_size, mean, std, expand_scale, canvas=1000, device="cuda:0", rng=random, seg_classes=None, seq=None, decoder=None,
+                 warp=None):
         self.sizes = [tuple(int(v) for v in s) for s in train_img_size]
         self.mean = (ctypes.c_float * 3)(*[float(v) for v in mean])
         self.std = (ctypes.c_float * 3)(*[float(v) for v in std])
@@ -254,6 +452,7 @@ class TrainAugment:
         self._seg_status = None
         self.seq = seq
         self.decoder = decoder
+        self.warp = warp
 
     @classmethod
     def from_config(cls, cfg, **kw):
@@ -400,12 +599,17 @@ class TrainAugment:
                             raise ValueError("seg_id must be uint8 [h,w] of the image's size %s, got %s %s" % (hw, sg.dtype, sg.shape))
             groups = [[m[:2] for m in g] for g in groups]
         members, samples, targets, n_mosaic = [], [], [], 0
+        hw_of = lambda im: (int(im[0]), int(im[1])) if isinstance(im, tuple) else (int(im.shape[0]), int(im.shape[1]))
+        wplan = None if self.warp is None else self.warp.plan([hw_of(m[0]) for g in groups for m in g])
         for gi, g in enumerate(groups):
             if not 1 <= len(g) <= 4:
                 raise ValueError("a group holds 1 to 4 images, got %d" % len(g))
             mems = []
             for im, tgt in g:
-                h, w = (int(im[0]), int(im[1])) if isinstance(im, tuple) else (int(im.shape[0]), int(im.shape[1]))
+                h, w = hw_of(im)
+                k = len(members) + len(mems)
+                if wplan is not None and not wplan["identity"][k]:
+                    tgt = self.warp.boxes(tgt, wplan["matrices"][k], h, w)
                 mems.append(self._member(h, w, tgt, len(g) == 1))
                 mems[-1]["src"] = (h, w)
             if len(g) == 1:
@@ -447,8 +651,11 @@ class TrainAugment:
                                      "area resize is not implemented)" % (k, m["geo"][0], m["geo"][1], gh, gw))
         max_h = int(max(items["exp"][:, 0].max(), items["h"].max()))
         max_w = int(max(items["exp"][:, 1].max(), items["w"].max()))
-        return dict(items=items, samples=np.array(samples, SAMPLE), targets=targets, count=sum(len(g) for g in groups),
-                    size=tuple(int(v) for v in size), n_mosaic=n_mosaic, max_h=max_h, max_w=max_w, members=members)
+        out = dict(items=items, samples=np.array(samples, SAMPLE), targets=targets, count=sum(len(g) for g in groups),
+                   size=tuple(int(v) for v in size), n_mosaic=n_mosaic, max_h=max_h, max_w=max_w, members=members)
+        if wplan is not None:
+            out["warp"] = wplan
+        return out
 
     # ---- device ---------------------------------------------------------------------------------------------------
     def run_device(self, src, plan, out=None):
@@ -536,18 +743,27 @@ class TrainAugment:
             src = stage.to(self.device, non_blocking=True)
         if self.seq is not None:
             src = self.seq.run_device(src, plan["items"], self.seq.plan(len(plan["items"])))
+        if self.warp is not None:
+            src = self.warp.run_device(src, plan["items"], plan["warp"], channels=3)
         if self.seg_classes is None:
             images = self.run_device(src, plan)
             return images, plan["targets"], plan["count"]
         seg_stage, seg_offsets = self.pack_seg(groups)
         images = self.run_device(src, plan)
-        seg_maps = self.run_device_seg(seg_stage.to(self.device, non_blocking=True), seg_offsets, plan, items_dev=self._keep[1], samples_dev=self._keep[2])
+        seg_src = seg_stage.to(self.device, non_blocking=True)
+        if self.warp is not None:                                        # the id maps take the image's coefficients
+            seg_desc = np.zeros(len(plan["items"]), DESC)
+            seg_desc["offset"], seg_desc["h"], seg_desc["w"] = seg_offsets, plan["items"]["h"], plan["items"]["w"]
+            seg_src = self.warp.run_device(seg_src, seg_desc, plan["warp"], channels=1)
+        seg_maps = self.run_device_seg(seg_src, seg_offsets, plan, items_dev=self._keep[1], samples_dev=self._keep[2])
         return images, plan["targets"], plan["count"], seg_maps
 
     def check(self):
         """Host sync: raise if the last batch held an image or record outside the declared bounds."""
         if self.seq is not None:
             self.seq.check()
+        if self.warp is not None:
+            self.warp.check()
         if self._status is not None:
             v = int(self._status.item())
             if v > 0:

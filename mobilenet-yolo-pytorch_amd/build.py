@@ -16,7 +16,7 @@ BASE_FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wall", "
 # detect.hip must round like the CPU kernels it replaces (bit-exact NMS): no FMA contraction there
 EXTRA = {"detect.hip": ["-ffp-contract=off"], "evalmap.hip": ["-ffp-contract=off"], "prep.hip": ["-ffp-contract=off"],
          "augment.hip": ["-ffp-contract=off"], "augseq.hip": ["-ffp-contract=off"], "cocoeval.hip": ["-ffp-contract=off"],
-         "segeval.hip": ["-ffp-contract=off"], "anchors.hip": ["-ffp-contract=off"]}
+         "segeval.hip": ["-ffp-contract=off"], "anchors.hip": ["-ffp-contract=off"], "augwarp.hip": ["-ffp-contract=off"]}
 
 
 def sources():
