@@ -330,8 +330,9 @@ def test_fused_bn_backward_expand_unit_is_run_to_run_deterministic(ops, M, K, Nc
 def test_fused_dw5_stride2_unit_backward(ops, N, H, W, C, act, xact, dtype):
     """mny_dw_bnbwd_s2k5 == mny_bn_bwd_apply -> mny_dw_bwd_weight + mny_dw_bwd_data (the three launches it replaces) on the same inputs — fp32
     2e-4 relative; bf16 storage: dX within one rounding of the unfused path (which rounds dY to bf16 in between) — and, with the producer's
-    statistics, the same dX / dW plus partial rows that sum to mny_bn_bwd_reduce(dX, x).  Odd sizes, one-row images, several strips per
-    workgroup (40 x 64 x 64: 2 560 strips of 16 quad rows over 768 workgroups), 68 channel pairs (two channel chunks)."""
+    statistics, the same dX / dW plus partial rows that sum to mny_bn_bwd_reduce(dX, x).  Odd sizes, one-row images, the largest grid of
+    these cases (40 x 64 x 64 x 72: 2 560 strips of 16 quad rows, 7 per workgroup of 36 channel pairs = 368 workgroups under the cap of 768, so
+    every workgroup still takes ONE trip of its loop; second and third trips: test_gpu_dw_trips.py), 68 channel pairs (two channel chunks)."""
     import ctypes
     from mobilenet_yolo_pytorch_amd import _lib
     bf = dtype == "bf16"
