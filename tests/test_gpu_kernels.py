@@ -160,7 +160,8 @@ def test_bn_train_forward_backward(ops, N, H, W, C, act):
 
 
 @pytest.mark.parametrize("N,H,W,Co", [(2, 32, 32, 32), (3, 22, 18, 16), (1, 352, 352, 32), (2, 20, 26, 12), (2, 130, 70, 32),
-                                      (4, 512, 512, 16), (3, 100, 132, 32)])      # 1024 tiles > the 768 workgroups of the matrix-core weight gradient; ragged tiles
+                                      (4, 512, 512, 16), (3, 100, 132, 32),       # 1024 tiles > the 768 workgroups of the matrix-core weight gradient; ragged tiles
+                                      (3, 101, 133, 32), (2, 21, 27, 12), (2, 33, 35, 64)])     # odd H and W: the bottom / right zero padding is read
 def test_stem(ops, N, H, W, Co):
     x = rnd(N, 3, H, W, seed=1)
     w = rnd(Co, 3, 3, 3, seed=2, scale=0.3)
@@ -596,7 +597,8 @@ def test_dgrad_with_fused_bn_backward_reduction(ops, M, K, Nc, act):
 
 @pytest.mark.parametrize("N,H,W,Co,act,dtype", [(2, 32, 32, 32, 1, torch.float32), (3, 22, 18, 16, 2, torch.float32), (1, 130, 70, 32, 1, torch.float32),
                                                  (2, 64, 64, 16, 1, torch.bfloat16), (4, 512, 512, 16, 4, torch.bfloat16), (2, 100, 132, 16, 4, torch.bfloat16),
-                                                 (3, 70, 50, 32, 4, torch.bfloat16)])
+                                                 (3, 70, 50, 32, 4, torch.bfloat16),
+                                                 (3, 101, 133, 32, 1, torch.float32), (3, 101, 132, 16, 4, torch.bfloat16), (2, 33, 35, 64, 1, torch.float32)])    # odd sizes
 def test_stem_weight_gradient_with_fused_bn_backward(ops, N, H, W, Co, act, dtype):
     """mny_stem_bnwgrad(x, G, Y) == mny_bn_bwd_apply -> mny_stem_wgrad on the same inputs (and the same dgamma / dbeta)."""
     x = rnd(N, 3, H, W, seed=1).cuda()
@@ -615,7 +617,8 @@ def test_stem_weight_gradient_with_fused_bn_backward(ops, N, H, W, Co, act, dtyp
 
 
 @pytest.mark.parametrize("N,H,W,Co,act,dtype", [(5, 256, 320, 16, 4, torch.bfloat16), (2, 100, 132, 16, 4, torch.float32), (3, 70, 50, 32, 1, torch.bfloat16),
-                                                 (2, 96, 96, 32, 1, torch.float32)])
+                                                 (2, 96, 96, 32, 1, torch.float32),
+                                                 (3, 101, 133, 32, 1, torch.float32), (3, 101, 132, 16, 4, torch.bfloat16)])      # odd sizes: W % 4 == 1, and the float4 staging
 def test_stem_weight_gradient_on_the_matrix_cores_against_fp64(N, H, W, Co, act, dtype):
     """mny_stem_bnwgrad (stem_wgrad_mfma_kernel for Cout 16 / 32: dY rebuilt from (G, Y, coef), reduction over the pixels on
     v_mfma_f32_16x16x4_f32) against an fp64 weight gradient of the fp64-rebuilt dY: ragged tiles, W % 4 != 0, several tiles per workgroup."""

@@ -74,7 +74,8 @@ def test_project_unit_backward_in_one_pass(M, Ki, No, act):
         assert e <= 2e-4 * ref.abs().max().item() + 1e-3, (name, e, ref.abs().max().item())
 
 
-@pytest.mark.parametrize("M,Ki,No", [(40000, 32, 16), (20000, 144, 24), (12345, 192, 32)])
+@pytest.mark.parametrize("M,Ki,No", [(40000, 32, 16), (20000, 144, 24), (12345, 192, 32),
+                                     (65619, 96, 16), (131155, 32, 24)])      # above the grid's cap: three trips, six tiles in the last, three pixels in the last tile
 def test_project_unit_backward_equals_the_three_launches(M, Ki, No):
     """mny_bn_bwd_apply -> mny_pw_dgrad_bnred (+ its BN sums) -> mny_pw_wgrad on the same inputs."""
     dev = torch.device("cuda:0")
