@@ -40,8 +40,9 @@ def make_case(M, C, R, seed, residual):
     add = None
     if residual == "real":
         add = (torch.randn(M, C, generator=g).to(torch.bfloat16), None, None, 0)
-    elif residual == "view":
-        add = (torch.randn(M, C, generator=g).to(torch.bfloat16), torch.rand(C, generator=g) + 0.5, torch.randn(C, generator=g) * 0.2, 0)
+    elif residual in ("view", "view-relu"):               # the second: the operand is the ACTIVATED view of a unit's raw output
+        add = (torch.randn(M, C, generator=g).to(torch.bfloat16), torch.rand(C, generator=g) + 0.5, torch.randn(C, generator=g) * 0.2,
+               _lib.ACT_RELU if residual == "view-relu" else 0)
     return y3, s3, b3, w1, w2, g1, be1, g2, be2, add
 
 
@@ -65,7 +66,8 @@ def ref_forward(y3, s3, b3, w1, w2, g1, be1, g2, be2, add, dtype=torch.float64):
         a = add[0].float().to(dtype)
         if add[1] is not None:
             a = a * add[1].to(dtype) + add[2].to(dtype)
-        out = out + a
+        assert add[3] in (0, _lib.ACT_RELU)
+        out = out + (torch.relu(a) if add[3] == _lib.ACT_RELU else a)
     return dict(h_raw=h_raw, g_raw=g_raw, m1=m1, v1=v1, m2=m2, v2=v2, sc1=sc1, sh1=sh1, sc2=sc2, sh2=sh2, out=out)
 
 
@@ -111,7 +113,8 @@ def run_forward(case, C, R):
 
 
 @pytest.mark.parametrize("C,R", SHAPES)
-@pytest.mark.parametrize("M,residual", [(16 * 37 + 5, None), (4096, "real"), (64 * 64 * 3, "view"), (32768 * 2 + 21, "view")])      # the last: above the capped grid (32 768 pixels), ragged — every workgroup accumulates several 16-pixel tiles into its partial row
+@pytest.mark.parametrize("M,residual", [(16 * 37 + 5, None), (4096, "real"), (64 * 64 * 3, "view"), (32768 * 2 + 21, "view"),
+                                        (169, "view-relu"), (32915, "view-relu")])      # (169, 32915: gate_regimes.TABLE's g-wave and g-trip2) the fourth: above the capped grid (32 768 pixels), ragged — every workgroup accumulates several 16-pixel tiles into its partial row
 def test_gate_forward_matches_torch(C, R, M, residual):
     case = make_case(M, C, R, seed=C + M, residual=residual)
     ref = ref_forward(*case)
@@ -163,7 +166,7 @@ def ref_backward(case, dout):
 
 
 @pytest.mark.parametrize("C,R", SHAPES)
-@pytest.mark.parametrize("M", [16 * 37 + 5, 128 * 40, 32768 * 2 + 21])          # the last: above the capped grid, ragged (multi-tile accumulation of the partial rows and dW partials, tail masking)
+@pytest.mark.parametrize("M", [16 * 37 + 5, 128 * 40, 32768 * 2 + 21, 169, 32915])          # the third: above the capped grid, ragged (multi-tile accumulation of the partial rows and dW partials, tail masking)
 def test_gate_backward_matches_autograd(C, R, M):
     dev = torch.device("cuda:0")
     case = make_case(M, C, R, seed=3 * C + M, residual=None)
