@@ -6,7 +6,10 @@ With --seg C the config gets a `seg:` section of C classes (the BDD100K config h
 logits are scored against full-resolution id maps by segeval.SegEvaluator: per-class IoU, mIoU, pixel accuracy — no seg map is
 copied to the host except the reference's own seg_out of image 0.
 
-    python examples/eval_synthetic.py [--images 256] [--batch 64] [--size 352] [--seg 2]
+With --report the same detections also give the validation report: per-class precision / recall / F1 at the confidence that maximises
+the smoothed mean F1 (a threshold on obj * cls_conf, the score the metrics use), and the detection confusion matrix.
+
+    python examples/eval_synthetic.py [--images 256] [--batch 64] [--size 352] [--seg 2] [--report]
 """
 import argparse
 import os
@@ -38,12 +41,29 @@ def id_maps(sizes, n_classes, seed):
     return out
 
 
+def print_report(rep, names):
+    """the table current YOLO trainers print per epoch, at the confidence that maximises the smoothed mean F1"""
+    print("REPORT best_conf %.3f (on obj * cls_conf)  P %.4f  R %.4f  F1 %.4f" % (rep["best_conf"], rep["P"], rep["R"], rep["F1"]))
+    print("  %-10s %8s %8s %8s %8s" % ("class", "P", "R", "F1", "objects"))
+    for n in names:
+        P, R, F1, n_pos = rep["per_class"][n]
+        print("  %-10s %8.4f %8.4f %8.4f %8d" % (n, P, R, F1, n_pos) if n_pos else "  %-10s %8s %8s %8s %8d" % (n, "-", "-", "-", 0))
+    cm = rep["confusion"]
+    K = cm.shape[0] - 1
+    print("  confusion (rows predicted, columns true, last = background): %d matched on the diagonal, %d off it, %d missed, %d false positives" % (
+        int(np.trace(cm[:K, :K])), int(cm[:K, :K].sum() - np.trace(cm[:K, :K])), int(cm[K, :K].sum()), int(cm[:K, K].sum())))
+    with np.printoptions(linewidth=250):
+        print(cm)
+    assert cm[K, K] == 0 and 0.0 <= rep["best_conf"] <= 1.0 and len(rep["per_class"]) == K
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--images", type=int, default=256)
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--size", type=int, default=352)
     ap.add_argument("--seg", type=int, default=0, help="classes of a segmentation head (0: the VOC config, no head)")
+    ap.add_argument("--report", action="store_true", help="print the P / R / F1 table at the best confidence and the confusion matrix")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
@@ -78,6 +98,8 @@ def main():
     coco = ev.compute_coco(image_size=(a.size, a.size))                            # COCO protocol on the same detections, network input pixels
     print("COCO  " + "  ".join("%s %.4f" % (k, v) for k, v in coco.items() if k != "per_class_AP"))
     assert len(coco["per_class_AP"]) == 20 and all(v == -1 or 0.0 <= v <= 1.0 for k, v in coco.items() if k != "per_class_AP")
+    if a.report:
+        print_report(ev.compute_report(image_size=(a.size, a.size)), classes_name[1:])
     if seg_ev is not None:
         seg = seg_ev.compute()                                                     # the one host sync of the seg leg
         print("SEG   " + "  ".join("IoU[%s] %.4f" % kv for kv in seg["iou"].items())

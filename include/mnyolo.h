@@ -554,6 +554,64 @@ int mny_coco_eval(const float* det_boxes /*[D,4]*/, const float* det_labels, con
                   const int32_t* stat_desc /*[S,4]*/, int S, double* precision, double* recall, double* stats,
                   double* per_class_ap, int32_t* det_match, uint8_t* det_ignore, void* ws, void* stream);
 
+/* ---- validation report on the device (csrc/detreport.hip) ----------------------------------------------
+ * Precision / recall / F1 of every class over a grid of confidences, the confidence that maximises the
+ * smoothed mean F1, and a detection confusion matrix.  Nothing in the reference computes them and no third-
+ * party package is pinned: the rules below (restated in numpy, float64, in tests/report_ref.py) are the
+ * specification.  The curves are exact step functions of the detection set { score >= c }; the np.interp of
+ * other trainers' curves is not reproduced.  All fp64 arithmetic is done as separate IEEE operations in the
+ * order written (the file is compiled with -ffp-contract=off); integer counts are exact.
+ *
+ * mny_det_curves.  Inputs (device): det_labels[D], det_scores[D]; det_match[D] (int32: >= 0 matched, -1
+ *   unmatched, -2 not evaluated) and det_ignore[D] (uint8), one [area, iou] slice of mny_coco_eval's optional
+ *   outputs; true_labels[T], true_crowd[T].  K = n_classes-1 classes (n_classes counts the background entry,
+ *   2..255), a grid of G points (2..4096), an odd smoothing window W (1..G).
+ *   A detection counts if its label is an integer in 1..K, det_match != -2 and det_ignore == 0; it is a TP
+ *   if det_match >= 0, else an FP.  npos[k] = ground truths with label k+1 and true_crowd == 0.
+ *   c_j = (double)j / (G-1).  tp[k,j] / fp[k,j] = counted TPs / FPs of class k+1 with (double)score >= c_j
+ *   (a NaN score is counted nowhere, a score above 1 everywhere).
+ *   P = tp/(tp+fp), 1.0 where tp+fp == 0; R = tp/npos; F1 = ((2.0*P)*R)/((P+R)+1e-16); with npos[k] == 0 all
+ *   three are -1 and the class is left out of every mean.  mean_f1[j] = (sum of F1 over the classes with
+ *   positives, ascending k, starting from 0.0) / their number, -1 without any.  smooth_f1[j] = (sum of
+ *   mean_f1[clamp(i, 0, G-1)] for i = j-W/2 .. j+W/2, ascending, starting from 0.0) / W.  best = the first j
+ *   that maximises smooth_f1; best_conf = c_best.  at_best[K+1,3] = (P, R, F1) of each class at best; row K =
+ *   their means over the classes with positives (same order and start), -1 without any.
+ *   Outputs (device): tp, fp [K,G] int64; npos[K] int64; precision, recall, f1 [K,G] fp64; mean_f1[G],
+ *   smooth_f1[G] fp64; best[1] int32; best_conf[1] fp64; at_best[(K+1)*3] fp64.
+ *   D == 0 and T == 0 are valid.  D, T <= 2^30; beyond the limits MNY_EINVAL with a mny_last_error text, and
+ *   mny_det_curves_ws_bytes returns 0.  ws: mny_det_curves_ws_bytes(D, T, n_classes, G, W) bytes.
+ *
+ * mny_det_confusion.  Inputs: the packed layout of mny_coco_eval (image_sizes NULL = (1, 1)), conf and
+ *   iou_thr (not NaN), accumulate (0: the matrix is zeroed first; 1: it is added to, one call per batch).
+ *   Per image: the detections are those with an integer label in 1..K and (double)score > conf; the ground
+ *   truths those with an integer label in 1..K, crowds included.  IoU: the geometry of mny_coco_eval with the
+ *   non-crowd union for every pair.  Candidates are the pairs with iou > iou_thr (a NaN IoU is none); classes
+ *   are not compared.  Repeatedly the candidate of largest IoU whose detection and ground truth are both free
+ *   is taken (among equal IoUs the smaller stored detection index, then the smaller ground-truth index) and
+ *   both are marked matched, until no candidate is left: at most min(detections, ground truths) rounds.
+ *   matrix[(K+1),(K+1)] int64, row = predicted class, column = true class, index K = background: a matched
+ *   non-crowd ground truth adds 1 at [pred-1][true-1], an unmatched non-crowd one at [K][true-1], an unmatched
+ *   detection at [pred-1][K]; a crowd ground truth and the detection matched to it add nothing; [K][K] stays
+ *   0.  Optional det_gt[D] (int32, stored order, NULL to skip): packed index of the matched ground truth, -1
+ *   unmatched, -2 not considered.  Boxes per image have no limit (an LDS table of IoUs for small images,
+ *   recomputation beyond it).  Limits: n_classes 2..255, n_images < 2^24, D, T <= 2^30; beyond them
+ *   MNY_EINVAL (mny_det_confusion_ws_bytes returns 0).  ws: mny_det_confusion_ws_bytes(D, T, n_images,
+ *   n_classes) bytes.
+ * Both: no host sync, no floating-point atomics (integer adds only), deterministic. */
+size_t mny_det_curves_ws_bytes(int64_t D, int64_t T, int n_classes, int G, int W);
+int mny_det_curves(const float* det_labels, const float* det_scores, const int32_t* det_match,
+                   const uint8_t* det_ignore, int64_t D, const float* true_labels, const float* true_crowd,
+                   int64_t T, int n_classes, int G, int W, int64_t* tp, int64_t* fp, int64_t* npos,
+                   double* precision, double* recall, double* f1, double* mean_f1, double* smooth_f1,
+                   int32_t* best, double* best_conf, double* at_best, void* ws, void* stream);
+size_t mny_det_confusion_ws_bytes(int64_t D, int64_t T, int n_images, int n_classes);
+int mny_det_confusion(const float* det_boxes /*[D,4]*/, const float* det_labels, const float* det_scores,
+                      const int32_t* det_off /*[n_images+1]*/, const float* true_boxes /*[T,4]*/,
+                      const float* true_labels, const float* true_crowd, const int32_t* true_off,
+                      const float* image_sizes /*[n_images,2], NULL = (1,1)*/, int n_images, int64_t D,
+                      int64_t T, int n_classes, double conf, double iou_thr, int accumulate, int64_t* matrix,
+                      int32_t* det_gt, void* ws, void* stream);
+
 /* ---- segmentation head of the BDD100K config ------------------------------------------------
  * Replaces SegLoss.forward (models/seg_loss.py:51-80) and its autograd on the channels-last seg head
  * [N,h,w,C] (the reference permutes seg_maps [N,h,w,C] to NCHW instead, :54): n = N*h*w*C elements.

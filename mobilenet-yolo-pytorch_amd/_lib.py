@@ -193,6 +193,11 @@ _SIGS["mny_anchor_kmeans"] = (c_int, [P, c_int64, P, c_int, c_int, P, P, P, P, P
 _SIGS["mny_anchor_fitness"] = (c_int, [P, c_int64, P, c_int, c_int, c_float, P, P, P])
 _SIGS["mny_anchor_evolve"] = (c_int, [P, c_int64, P, c_int, P, c_int, c_int, c_float, c_float, P, P, P, P])
 _SIGS["mny_anchor_census"] = (c_int, [P, c_int64, P, c_int, P, P, c_int, c_int, c_float, P, P])
+# validation report (csrc/detreport.hip)
+_SIGS["mny_det_curves_ws_bytes"] = (c_size_t, [c_int64, c_int64, c_int, c_int, c_int])
+_SIGS["mny_det_curves"] = (c_int, [P, P, P, P, c_int64, P, P, c_int64, c_int, c_int, c_int] + [P] * 13)
+_SIGS["mny_det_confusion_ws_bytes"] = (c_size_t, [c_int64, c_int64, c_int, c_int])
+_SIGS["mny_det_confusion"] = (c_int, [P] * 9 + [c_int, c_int64, c_int64, c_int, c_double, c_double, c_int, P, P, P, P])
 EXPORTS = tuple(_SIGS)
 
 _lib = None

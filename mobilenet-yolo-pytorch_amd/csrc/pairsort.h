@@ -1,4 +1,4 @@
-// Sort of (64-bit key, 32-bit value) pairs on the device, shared by the evaluation stages (evalmap.hip, cocoeval.hip).
+// Sort of (64-bit key, 32-bit value) pairs on the device, shared by the evaluation stages (evalmap.hip, cocoeval.hip, detreport.hip).
 // Everything sits in an unnamed namespace of namespace mny: every translation unit that includes it gets its own copy of the kernels.
 #pragma once
 #include "common.h"
@@ -8,7 +8,7 @@ namespace {
 
 // ---- sort of (key, value) pairs, ascending in (key, value) ----------------------------------------------------------------
 // The values of equal keys are distinct and ascend in stored order (evalmap.hip: stored detection index << 2 | flags; cocoeval.hip: the
-// index), so the pair order is total and equals the stable order by key.  Bitonic network
+// index; detreport.hip: index << 1 | TP), so the pair order is total and equals the stable order by key.  Bitonic network
 // over n2 = 2^m >= D padded pairs: every run of steps with partner distance < kSortChunk happens inside LDS (one workgroup per
 // 4096-pair chunk), the few steps with a longer distance are one global compare-exchange pass each (6 MB for VOC07-test).
 constexpr int kSortChunk = 4096;

@@ -7,6 +7,9 @@ detections stay in the packed [k,7] rows the NMS stage wrote and are converted b
 `coco_eval` / `Evaluator.compute_coco` score the same packed detections by the COCO protocol (AP over IoU 0.50:0.05:0.95, by
 object size, AR at 1 / 10 / 100 detections) over `mny_coco_eval` (csrc/cocoeval.hip); its arithmetic is specified in
 include/mnyolo.h and is not pinned against pycocotools.
+`det_curves` / `det_confusion` / `Evaluator.compute_report` turn the match flags `coco_eval` leaves on the device into per-class
+precision / recall / F1 curves, the confidence that maximises F1, and a detection confusion matrix (`mny_det_curves`,
+`mny_det_confusion`, csrc/detreport.hip).
 There is no CPU fallback: without libmnyolo.so every call raises MnyError.
 """
 import ctypes
@@ -116,6 +119,80 @@ def coco_eval(det_boxes, det_labels, det_scores, det_off, true_boxes, true_label
          _p(out.get("det_match")) if D else None, _p(out.get("det_ignore")) if D else None, ctypes.c_void_p(ws.data_ptr()), _st())
     out["_keepalive"] = (args, ws)
     return out
+
+
+def det_curves(det_labels, det_scores, det_match, det_ignore, true_labels, true_crowd, n_classes, grid=1000, smooth=101):
+    """Precision / recall / F1 of every class over `grid` confidences c_j = j / (grid-1), and the confidence that maximises the mean F1
+    smoothed over an odd window of `smooth` points (`mny_det_curves`, csrc/detreport.hip; specified in include/mnyolo.h).  det_match [D]
+    int32 / det_ignore [D] uint8 are one [area, iou] slice of `coco_eval(..., matches=True)`.  The curves are exact step functions of the
+    set {score >= c}.  -> dict of device tensors: tp, fp [K,G] int64; npos [K] int64; precision, recall, f1 [K,G], mean_f1, smooth_f1 [G]
+    float64 (-1: class without positives); best [1] int32, best_conf [1] float64, at_best [K+1,3] = (P, R, F1) per class at `best`, last
+    row their means.  No host sync."""
+    if not 2 <= int(n_classes) <= 255:
+        raise ValueError("n_classes %d outside 2..255 (it counts the background entry)" % n_classes)
+    G, W = int(grid), int(smooth)
+    if not 2 <= G <= 4096:
+        raise ValueError("grid %d outside 2..4096" % G)
+    if not (1 <= W <= G and W % 2 == 1):
+        raise ValueError("smooth %d is not an odd number in 1..grid" % W)
+    D, T = int(det_labels.numel()), int(true_labels.numel())
+    if not (det_scores.numel() == det_match.numel() == det_ignore.numel() == D) or true_crowd.numel() != T:
+        raise ValueError("det_labels / det_scores / det_match / det_ignore, or true_labels / true_crowd, differ in length")
+    dev = det_labels.device
+    if dev.type != "cuda":
+        raise RuntimeError("det_curves needs CUDA tensors (the HIP path is the only path)")
+    args = [_f32(det_labels), _f32(det_scores), det_match.to(torch.int32).contiguous(), det_ignore.to(torch.uint8).contiguous(),
+            _f32(true_labels), _f32(true_crowd)]
+    K = int(n_classes) - 1
+    nb = query("mny_det_curves_ws_bytes", D, T, int(n_classes), G, W)
+    ws = torch.empty(max(int(nb), 256), device=dev, dtype=torch.uint8)
+    i64 = lambda *s: torch.empty(*s, device=dev, dtype=torch.int64)
+    f64 = lambda *s: torch.empty(*s, device=dev, dtype=torch.float64)
+    out = {"tp": i64(K, G), "fp": i64(K, G), "npos": i64(K), "precision": f64(K, G), "recall": f64(K, G), "f1": f64(K, G), "mean_f1": f64(G),
+           "smooth_f1": f64(G), "best": torch.empty(1, device=dev, dtype=torch.int32), "best_conf": f64(1), "at_best": f64(K + 1, 3)}
+    call("mny_det_curves", _p(args[0]), _p(args[1]), _p(args[2]), _p(args[3]), D, _p(args[4]), _p(args[5]), T, int(n_classes), G, W,
+         *[_p(out[k]) for k in ("tp", "fp", "npos", "precision", "recall", "f1", "mean_f1", "smooth_f1", "best", "best_conf", "at_best")],
+         ctypes.c_void_p(ws.data_ptr()), _st())
+    out["_keepalive"] = (args, ws)
+    return out
+
+
+def det_confusion(det_boxes, det_labels, det_scores, det_off, true_boxes, true_labels, true_crowd, true_off, n_classes, image_sizes=None,
+                  conf=0.25, iou_thr=0.45, out=None):
+    """Detection confusion matrix of packed inputs (the layout of `coco_eval`) on one CUDA device (`mny_det_confusion`, csrc/detreport.hip):
+    per image the detections with score > conf are matched one-to-one to the ground truths, classes not compared, largest IoU > iou_thr
+    first.  -> dict of device tensors: matrix [K+1,K+1] int64 (row = predicted class, column = true class, index K = background), det_gt [D]
+    int32 (packed index of the matched ground truth, -1 unmatched, -2 not considered).  out= a matrix of an earlier call: it is added to
+    and returned, so a loop can call this once per batch.  No host sync."""
+    if not 2 <= int(n_classes) <= 255:
+        raise ValueError("n_classes %d outside 2..255 (it counts the background entry)" % n_classes)
+    conf, iou_thr = float(conf), float(iou_thr)
+    if not 0.0 <= conf <= 1.0:
+        raise ValueError("conf %r outside 0..1" % conf)
+    if not 0.0 <= iou_thr <= 1.0:
+        raise ValueError("iou_thr %r outside 0..1" % iou_thr)
+    n_img = int(det_off.numel()) - 1
+    if true_off.numel() != n_img + 1:
+        raise ValueError("det_off and true_off describe different numbers of images")
+    if image_sizes is not None and tuple(image_sizes.shape) != (n_img, 2):
+        raise ValueError("image_sizes must be [n_images, 2] = (w, h)")
+    K = int(n_classes) - 1
+    dev = det_off.device
+    if dev.type != "cuda":
+        raise RuntimeError("det_confusion needs CUDA tensors (the HIP path is the only path)")
+    if out is not None and (tuple(out.shape) != (K + 1, K + 1) or out.dtype != torch.int64 or out.device != dev or not out.is_contiguous()):
+        raise ValueError("out must be a contiguous int64 [%d,%d] matrix on %s" % (K + 1, K + 1, dev))
+    D, T = int(det_labels.numel()), int(true_labels.numel())
+    args = [_f32(det_boxes), _f32(det_labels), _f32(det_scores), det_off.to(torch.int32).contiguous(),
+            _f32(true_boxes), _f32(true_labels), _f32(true_crowd), true_off.to(torch.int32).contiguous(),
+            _f32(image_sizes) if image_sizes is not None else None]
+    nb = query("mny_det_confusion_ws_bytes", D, T, n_img, int(n_classes))
+    ws = torch.empty(max(int(nb), 256), device=dev, dtype=torch.uint8)
+    matrix = out if out is not None else torch.empty(K + 1, K + 1, device=dev, dtype=torch.int64)
+    det_gt = torch.empty(max(D, 1), device=dev, dtype=torch.int32)[:D]
+    call("mny_det_confusion", *[_p(a) for a in args], n_img, D, T, int(n_classes), conf, iou_thr, 1 if out is not None else 0, _p(matrix),
+         _p(det_gt), ctypes.c_void_p(ws.data_ptr()), _st())
+    return {"matrix": matrix, "det_gt": det_gt, "_keepalive": (args, ws)}
 
 
 def _pack_list(ts, width, dev):
@@ -245,6 +322,44 @@ class Evaluator:
         out = dict(zip(COCO_STAT_NAMES, r["stats"].tolist()))
         out["per_class_AP"] = dict(zip(self.classes_name[1:], r["per_class_ap"].tolist()))
         return out
+
+    def compute_report_device(self, image_size=None, iou=0.5, max_det=100, device=None, **params):
+        """Validation report on the device, no host sync: `coco_eval` at the one threshold `iou`, all areas and at most `max_det`
+        detections per (image, class) gives the match flags; `det_curves` turns them into P / R / F1 curves and the best confidence;
+        `det_confusion` builds the confusion matrix.  **params: grid, smooth (det_curves), conf, iou_thr (det_confusion).
+        -> {"curves": dict of det_curves, "confusion": dict of det_confusion, "coco": dict of coco_eval}."""
+        cp = {k: params.pop(k) for k in ("grid", "smooth") if k in params}
+        fp = {k: params.pop(k) for k in ("conf", "iou_thr") if k in params}
+        if params:
+            raise TypeError("compute_report: unknown parameters %s" % sorted(params))
+        if image_size is None and any(s is None for s in self.sizes):
+            raise ValueError("compute_report needs image_size=(W, H), or sizes= at every add()")
+        sizes = [s if s is not None else (float(image_size[0]), float(image_size[1])) for s in self.sizes]
+        db, dl, ds, do, tb, tl, _, to = self._packed(device)
+        dev = do.device
+        crowd = (torch.cat(self.crowd) if self.crowd else torch.zeros(0)).to(dev)
+        isz = torch.tensor(sizes, dtype=torch.float32).reshape(-1, 2).to(dev)
+        nc = len(self.classes_name)
+        coco = coco_eval(db, dl, ds, do, tb, tl, crowd, to, nc, image_sizes=isz, iou_thrs=[float(iou)], area_rngs=[[0, 1e10]],
+                         max_dets=[int(max_det)], stat_desc=[[0, 0, 0, 0]], matches=True)
+        curves = det_curves(dl, ds, coco["det_match"][0, 0], coco["det_ignore"][0, 0], tl, crowd, nc, **cp)
+        confusion = det_confusion(db, dl, ds, do, tb, tl, crowd, to, nc, image_sizes=isz, **fp)
+        return {"curves": curves, "confusion": confusion, "coco": coco}
+
+    def compute_report(self, image_size=None, iou=0.5, max_det=100, device=None, **params):
+        """-> {"best_conf", "P", "R", "F1" (means over the classes with positives at best_conf; -1 without any), "per_class": {name: (P, R,
+        F1, n_pos)}, "confusion": int64 ndarray [K+1,K+1] (row = predicted, column = true, last = background), "curves": {"conf",
+        "precision", "recall", "f1", "mean_f1", "smooth_f1", "tp", "fp"} as ndarrays}.  best_conf is a threshold on the score the metrics
+        use, obj * cls_conf."""
+        r = self.compute_report_device(image_size, iou, max_det, device, **params)
+        c = {k: v.cpu().numpy() for k, v in r["curves"].items() if not k.startswith("_")}
+        G = c["mean_f1"].shape[0]
+        at, npos, names = c["at_best"], c["npos"], self.classes_name[1:]
+        curves = {k: c[k] for k in ("precision", "recall", "f1", "mean_f1", "smooth_f1", "tp", "fp")}
+        curves["conf"] = np.arange(G, dtype=np.float64) / (G - 1)
+        return {"best_conf": float(c["best_conf"][0]), "P": float(at[-1, 0]), "R": float(at[-1, 1]), "F1": float(at[-1, 2]),
+                "per_class": {n: (float(at[k, 0]), float(at[k, 1]), float(at[k, 2]), int(npos[k])) for k, n in enumerate(names)},
+                "confusion": r["confusion"]["matrix"].cpu().numpy(), "curves": curves}
 
     def compute(self, device=None):
         r = self.compute_device(device)
