@@ -231,6 +231,55 @@ size_t mny_nms_ws_bytes(int S, int capacity, int num_classes);
 size_t mny_nms_status_offset(int S, int capacity, int num_classes);
 size_t mny_nms_prefix_offset(int S, int capacity, int num_classes);
 
+/* ---- test-time augmentation of the detection path (csrc/tta.hip; Ultralytics' `--augment` and merge-NMS) ----
+ * The batch goes through the network as several views (sizes, some mirrored); every view's decoded candidates
+ * are appended, un-mirrored, into one segment per image, ONE per-class NMS runs over the union, and optionally
+ * every kept box is replaced by the score-weighted mean of the candidates of its class that overlap it.  The
+ * rows are normalised (mny_yolo_decode), so a change of scale needs no box arithmetic.  No host sync, no
+ * atomics, results bit-reproducible; tests/tta_ref.py restates the three stages in numpy.
+ *
+ * mny_tta_view: src[N,C,Hs,Ws] fp32 NCHW -> dst[N,C,Hd,Wd]: mirror, then bilinear resize with half-pixel
+ *   centres and no antialiasing (F.interpolate(mode="bilinear", align_corners=False) semantics), in fp64:
+ *     sy = max((y + 0.5) * ((double)Hs / Hd) - 0.5, 0);  y0 = (int)sy;  y1 = min(y0 + 1, Hs - 1);  ly = sy - y0
+ *     (the same for x with Ws, Wd: sx, x0, x1, lx);  with `flip` source column c is read from Ws - 1 - c;
+ *     a, b = src[y0][x0], src[y0][x1];  c, d = src[y1][x0], src[y1][x1], promoted to double;
+ *     dst[y][x] = (float)((1-ly) * ((1-lx)*a + lx*b) + ly * ((1-lx)*c + lx*d)): every product and sum one fp64
+ *     operation (no contraction), one rounding at the end.  A term whose weight is exactly 0 is skipped, not
+ *     multiplied, at both levels (a sum with one term left is that term's product): a non-finite neighbour
+ *     cannot poison an exact sample, and Hd == Hs, Wd == Ws is an exact (mirrored) copy.
+ *   Any sizes >= 1 are legal (the multiple-of-32 rule belongs to the network); src != dst.
+ *
+ * mny_det_append: rows are [.,7] as mny_yolo_decode writes them.  For image n:
+ *   copied = max(0, min(src_counts[n], src_stride, dst_stride - counts[n])) (0 when counts[n] is outside
+ *   0..dst_stride); rows src_rows[n*src_stride + r], r < copied, are written in source order to
+ *   dst_rows[n*dst_stride + counts[n] + r]; then counts[n] += copied.  With `flip` the written row has
+ *   x1' = 1.0f - x2 and x2' = 1.0f - x1 (one fp32 subtraction each); columns 1, 3 and 4..6 are copied.
+ *   The clamp keeps every write inside the image's segment; a caller that sizes dst_stride as the sum of its
+ *   sources' strides never meets it.  One workgroup per image.  N == 0 is valid.
+ *
+ * mny_nms_merge: runs after mny_nms_per_class (with out_rows) over the same rows and segments; out_prefix is
+ *   the int32[S+1] prefix that call leaves at ws + mny_nms_prefix_offset().  For segment s and
+ *   r < out_counts[s]: i = out_idx[seg_begin[s] + r] is a kept row, c = rows[i][6] its class, and its output
+ *   row is out_rows[out_prefix[s] + r].  Members: the rows j of segment s with rows[j][6] == c and
+ *   (j == i or (double)iou(i, j) > thr), where iou is the fp32 arithmetic of the NMS (kept box i first):
+ *     area = (x2 - x1) * (y2 - y1);  xx1 = i.x1 > j.x1 ? i.x1 : j.x1, yy1 likewise;
+ *     xx2 = i.x2 < j.x2 ? i.x2 : j.x2, yy2 likewise;  w = xx2 - xx1, h = yy2 - yy1, each set to 0 unless > 0
+ *     (negative or NaN);  inter = w * h;  iou = inter / (area_i + area_j - inter).
+ *   Weight w_j = rows[j][5] * rows[j][4] (one fp32 product, the NMS score).  In ascending j, in fp64:
+ *   sw += w_j;  sx_k += (double)w_j * (double)rows[j][k], k = 0..3 (the products are exact).  Then
+ *   out_rows[.][k] = (float)(sx_k / sw), or rows[i][k] when sw is not finite and positive.  Columns 4..6 and
+ *   the order of out_rows are untouched.  The summation order is part of the specification.
+ *   Design bound: segments of up to a few thousand rows — one lane per kept box walks its whole segment
+ *   (staged through LDS in chunks of 256 rows), time O(kept x rows) per segment on at most 8 workgroups;
+ *   larger segments are correct, only slow.  S == 0, empty segments and out_counts == 0 are valid. */
+int mny_tta_view(const float* src, float* dst, int N, int C, int Hs, int Ws, int Hd, int Wd, int flip,
+                 void* stream);
+int mny_det_append(const float* src_rows, int src_stride, const int32_t* src_counts, int flip,
+                   float* dst_rows, int dst_stride, int32_t* counts, int N, void* stream);
+int mny_nms_merge(const float* rows, const int32_t* seg_begin, const int32_t* seg_count, int S,
+                  const int32_t* out_idx, const int32_t* out_counts, const int32_t* out_prefix, double thr,
+                  float* out_rows, void* stream);
+
 /* ---- fused backward of a depthwise 3x3 stride-1 conv + BN + activation unit ----------------------------
  * One pass over (g, y, x) instead of bn_bwd_apply + dw_bwd_weight + dw_bwd_data (7 tensor passes -> 4): rebuilds
  * dY = ca*g*act'(scale*y+shift) + cb*y + cc in registers from the coefficients `coef` = [3][C] written by

@@ -198,6 +198,10 @@ _SIGS["mny_det_curves_ws_bytes"] = (c_size_t, [c_int64, c_int64, c_int, c_int, c
 _SIGS["mny_det_curves"] = (c_int, [P, P, P, P, c_int64, P, P, c_int64, c_int, c_int, c_int] + [P] * 13)
 _SIGS["mny_det_confusion_ws_bytes"] = (c_size_t, [c_int64, c_int64, c_int, c_int])
 _SIGS["mny_det_confusion"] = (c_int, [P] * 9 + [c_int, c_int64, c_int64, c_int, c_double, c_double, c_int, P, P, P, P])
+# test-time augmentation (csrc/tta.hip)
+_SIGS["mny_tta_view"] = (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P])
+_SIGS["mny_det_append"] = (c_int, [P, c_int, P, c_int, P, c_int, P, c_int, P])
+_SIGS["mny_nms_merge"] = (c_int, [P, P, P, c_int, P, P, P, c_double, P, P])
 EXPORTS = tuple(_SIGS)
 
 _lib = None

@@ -696,6 +696,7 @@ class NetPlan:
                          self.rows, self.cap, None, self.cnt0, self.stream)
             self.det.add("mny_yolo_decode", self.heads[1], self.anchors[1], self.masks[1], ctypes.byref(self.hp[1]), self.val_conf[1],
                          self.rows, self.cap, self.cnt0, self.cnt1, self.stream)
+            self.det_nms = len(self.det.calls)      # index of the NMS call (forward_eval(nms=False) steps over it)
             self.det.add("mny_nms_per_class", self.rows, self.seg_begin, self.cnt1, N, N * self.cap, self.cap, C, ctypes.c_double(0.45),
                          self.out_idx, self.out_counts, self.out_rows, self.nms_ws, self.stream)
             so = _lib.query("mny_nms_status_offset", N, N * self.cap, C)
@@ -1661,9 +1662,15 @@ class NetPlan:
         t, self.timing = self.timing, None
         return t
 
-    def forward_eval(self, x, val_conf):
+    def forward_eval(self, x, val_conf, nms=True):
+        """`nms=False` leaves the plan's own NMS out (the caller runs one over several plans' candidates, tta.py): rows / cnt1 hold the
+        decoded candidates, out_idx / out_counts / out_rows are not written."""
         x = self._bind(x)
         self.fwd.run()
         for i in range(2):
             self.val_conf[i].value = val_conf[i]
-        self.det.run()
+        if nms:
+            self.det.run()
+        else:
+            self.det.run(0, self.det_nms)
+            self.det.run(self.det_nms + 1)

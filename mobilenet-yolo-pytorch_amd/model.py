@@ -414,6 +414,17 @@ class yolo(nn.Module):
             return dets, plan.seg_eval.cpu().numpy()                            # (output, seg_out) mbv2_yolo.py:161-164
         return dets
 
+    def _eval_plans(self, N, sizes, img_hw):
+        """The cached eval plans (running statistics) of several square input sizes for one batch, for a caller that runs more than one view
+        per batch (tta.py).  Views of one size share a plan, whose resident buffers every replay overwrites: the caller takes what it needs
+        from a plan before it runs the next view, and seg_logits() of an earlier model(images) call is withdrawn.  `yolo_losses[i].img_size`
+        is left at img_hw, as a forward at that size leaves it (a plan build sets its own size)."""
+        plans = [self._plan(N, s, s, False) for s in sizes]
+        for hs in self.yolo_losses:
+            hs.img_size = list(img_hw)                                          # mbv2_yolo.py:139-140
+        self._eval_plan = None
+        return plans
+
     def seg_logits(self):
         """The seg head's raw logits of the last eval forward, [N,h,w,C] fp32 on the device (all N images: the (dets, seg_out) return
         keeps the reference's sigmoid of image 0 only).  A clone: the plan's buffer is overwritten by the next forward.  Feed it to

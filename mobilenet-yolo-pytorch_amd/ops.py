@@ -314,3 +314,38 @@ def nms_per_class(rows, seg_begin, seg_count, num_classes, thr=0.45, max_seg_row
     status = ws[so:so + 4].view(torch.int32)
     prefix = ws[po:po + 4 * (S + 1)].view(torch.int32)
     return out_idx, out_counts, out_rows, prefix, status
+
+
+# ---- test-time augmentation (csrc/tta.hip) ----------------------------------------------------------
+def tta_view(src, Hd, Wd, flip=False, out=None):
+    """src [N,C,Hs,Ws] fp32 NCHW -> [N,C,Hd,Wd]: mirrored (flip) then resized bilinearly, half-pixel centres, fp64 arithmetic."""
+    N, C, Hs, Ws = src.shape
+    assert src.dtype == torch.float32, "tta_view takes the fp32 input batch"
+    dst = out if out is not None else _new(N, C, int(Hd), int(Wd), like=src)
+    assert tuple(dst.shape) == (N, C, int(Hd), int(Wd)) and dst.dtype == torch.float32
+    call("mny_tta_view", _p(src), _p(dst), N, C, Hs, Ws, int(Hd), int(Wd), int(bool(flip)), _st())
+    return dst
+
+
+def det_append(src_rows, src_counts, dst_rows, counts, flip=False):
+    """Append image n's first src_counts[n] rows of src_rows [N,src_stride,7] behind the counts[n] rows of dst_rows [N,dst_stride,7]
+    (x un-mirrored with `flip`); counts is updated in place.  -> counts"""
+    N = counts.numel()
+    assert src_rows.dim() == 3 and dst_rows.dim() == 3 and src_rows.shape[2] == 7 and dst_rows.shape[2] == 7
+    assert src_rows.shape[0] == N and dst_rows.shape[0] == N and src_counts.numel() == N
+    assert src_rows.dtype == torch.float32 and dst_rows.dtype == torch.float32
+    assert src_counts.dtype == torch.int32 and counts.dtype == torch.int32
+    call("mny_det_append", _p(src_rows) if src_rows.numel() else None, src_rows.shape[1], _p(src_counts), int(bool(flip)),
+         _p(dst_rows) if dst_rows.numel() else None, dst_rows.shape[1], _p(counts), N, _st())
+    return counts
+
+
+def nms_merge(rows, seg_begin, seg_count, out_idx, out_counts, prefix, out_rows, thr=0.45):
+    """Behind nms_per_class(..., gather=True) on the same rows / segments: columns 0..3 of every kept row in out_rows become the
+    score-weighted mean of the candidates of its class with IoU > thr (and itself), in place.  -> out_rows"""
+    S = seg_begin.numel()
+    assert out_rows is not None and out_rows.dtype == torch.float32 and out_rows.shape[-1] == 7
+    assert all(t.dtype == torch.int32 for t in (seg_begin, seg_count, out_idx, out_counts, prefix)) and prefix.numel() == S + 1
+    call("mny_nms_merge", _p(rows) if rows.numel() else None, _p(seg_begin), _p(seg_count), S, _p(out_idx), _p(out_counts), _p(prefix),
+         float(thr), _p(out_rows), _st())
+    return out_rows
