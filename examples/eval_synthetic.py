@@ -9,7 +9,10 @@ copied to the host except the reference's own seg_out of image 0.
 With --report the same detections also give the validation report: per-class precision / recall / F1 at the confidence that maximises
 the smoothed mean F1 (a threshold on obj * cls_conf, the score the metrics use), and the detection confusion matrix.
 
-    python examples/eval_synthetic.py [--images 256] [--batch 64] [--size 352] [--seg 2] [--report]
+With --multi-label / --agnostic / --max-det K the detections come from postprocess.Detector instead of model(images): the Ultralytics
+protocol (conf and score threshold 0.001, a candidate per (box, class) pair, class-agnostic NMS, at most K detections per image).
+
+    python examples/eval_synthetic.py [--images 256] [--batch 64] [--size 352] [--seg 2] [--report] [--multi-label] [--agnostic] [--max-det 300]
 """
 import argparse
 import os
@@ -20,7 +23,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from mobilenet_yolo_pytorch_amd import synthetic, yolo  # noqa: E402
+from mobilenet_yolo_pytorch_amd import Detector, PostProcess, synthetic, yolo  # noqa: E402
 from mobilenet_yolo_pytorch_amd.evalmap import Evaluator, adjust_confidence  # noqa: E402
 from mobilenet_yolo_pytorch_amd.prep import BatchPrep  # noqa: E402
 from mobilenet_yolo_pytorch_amd.segeval import SegEvaluator  # noqa: E402
@@ -64,6 +67,9 @@ def main():
     ap.add_argument("--size", type=int, default=352)
     ap.add_argument("--seg", type=int, default=0, help="classes of a segmentation head (0: the VOC config, no head)")
     ap.add_argument("--report", action="store_true", help="print the P / R / F1 table at the best confidence and the confusion matrix")
+    ap.add_argument("--multi-label", action="store_true", help="a candidate per (box, class) pair with obj * cls > 0.001")
+    ap.add_argument("--agnostic", action="store_true", help="class-agnostic NMS")
+    ap.add_argument("--max-det", type=int, default=None, help="at most this many detections per image")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
@@ -71,6 +77,11 @@ def main():
     model = yolo(cfg).to(dev).eval()
     for hs in model.yolo_losses:
         hs.val_conf = 0.3
+    detect = model
+    if a.multi_label or a.agnostic or a.max_det is not None:
+        low = 0.001 if a.multi_label else None                                      # the protocol's low thresholds go with multi_label
+        detect = Detector(model, PostProcess(conf_thres=low, score_thres=low, multi_label=a.multi_label, agnostic=a.agnostic, max_det=a.max_det))
+        print("post-processing:", detect.post)
     classes_name = ["background"] + ["class%d" % i for i in range(1, 21)]          # train.py:57-58
     prep = BatchPrep([(a.size, a.size)], [0.485, 0.456, 0.406], [0.229, 0.224, 0.225], device=dev)
     ev = Evaluator(classes_name)
@@ -83,7 +94,7 @@ def main():
         photos = synthetic.photos(sizes, seed=b)                                   # "decoded JPEGs"
         targets = synthetic.targets(n, seed=b + 1, empty_every=8)
         images = prep(photos)                                                      # folder2lmdb.py:223-256 on the device
-        out = model(images)
+        out = detect(images)
         if seg_ev is not None:
             out = out[0]                                                           # (dets, seg_out of image 0): the reference's return
             seg_ev.add(model.seg_logits(), id_maps(sizes, a.seg, seed=b + 2))      # all n seg outputs, at each label's own size

@@ -280,6 +280,63 @@ int mny_nms_merge(const float* rows, const int32_t* seg_begin, const int32_t* se
                   const int32_t* out_idx, const int32_t* out_counts, const int32_t* out_prefix, double thr,
                   float* out_rows, void* stream);
 
+/* ---- post-processing options of the detection path (csrc/postproc.hip; Ultralytics' non_max_suppression protocol) ----
+ * Opt-in: mny_yolo_decode / mny_nms_per_class are what they were.  A score threshold, a candidate per (cell, class)
+ * pair (`multi_label`), a class filter, class-agnostic NMS and a cap on the detections per image (`max_det`).  The
+ * row format (x1, y1, x2, y2, conf, cls, class) is unchanged, so the NMS, mny_nms_merge and the evaluators read the
+ * rows as before.  No host sync, no atomics, results bit-reproducible; tests/post_ref.py restates the three stages.
+ *
+ * mny_yolo_decode_ex: head, anchors_all, mask, hp, rows, row_stride, base_counts and counts as mny_yolo_decode.
+ *   For image n and every cell in (anchor, gy, gx) order, with the arithmetic of mny_yolo_decode (one definition,
+ *   csrc/detshare.h): box = the decoded corners, conf = sigmoid(t4), cls_c = sigmoid(t[5+c]) with
+ *   sigmoid(x) = 1.0f / (1.0f + expf(-x)); b = the first c with the largest cls_c (a NaN never wins; b = 0 when no
+ *   cls_c exceeds -inf).  score_c = conf * cls_c, one fp32 product: the product the NMS forms from columns 4 and 5.
+ *     allowed(c) = class_mask == NULL or bit (c & 31) of class_mask[c >> 5] is set   (DEVICE uint32 words)
+ *     pass(c)    = conf > obj_thr and (score_thr < 0 or score_c > score_thr) and allowed(c)
+ *   All compares are strict and a NaN fails them; a negative score_thr switches the score test off.
+ *   multi_label == 0: the cell emits (box, conf, cls_b, b) when pass(b).
+ *   multi_label != 0: the cell emits (box, conf, cls_c, c) for every c with pass(c), c ascending.
+ *   Candidates are numbered t = 0, 1, ... in that order (cells, then classes).  base = base_counts[n] (NULL -> 0);
+ *   room = row_stride - base when 0 <= base <= row_stride, else 0.  Candidate t is written to
+ *   rows[n*row_stride + base + t] when t < room, and to nowhere otherwise: nothing is written outside the image's
+ *   segment.  counts[n] = base + min(total, room);  dropped[n] = total - min(total, room)  (DEVICE int32 [N]).
+ *   row_stride >= 1 is the only requirement; the caller checks `dropped` with the counts.  With multi_label = 0,
+ *   score_thr < 0, class_mask = NULL and row_stride >= A*g*g the rows and counts are mny_yolo_decode's bit for bit.
+ *
+ * mny_nms_agnostic: the result of mny_nms_per_class on the same rows with column 6 read as 0 and num_classes = 1
+ *   (one bucket per segment: descending score = rows[i][5] * rows[i][4], ties by original order; the same kernels,
+ *   a segment beyond the 8192-row LDS image goes through global scratch).  out_idx, out_counts, the prefix and the
+ *   status word are as there, under the offsets of mny_nms_agnostic_*_offset(); out_rows carries the ORIGINAL rows,
+ *   class included.  ws: mny_nms_agnostic_ws_bytes() bytes.
+ *
+ * mny_det_topk: runs after either NMS (same rows, seg_begin, capacity) and before mny_nms_merge; in place on
+ *   out_idx / out_counts / out_rows.  For segment s: k = out_counts[s] clamped to 0 .. capacity - seg_begin[s];
+ *   entry r < k is the row i_r = out_idx[seg_begin[s] + r] with score_r = rows[i_r][5] * rows[i_r][4] (one fp32
+ *   product; 0 when i_r is not in 0 .. capacity-1).  Order the entries by the NMS's own key, ascending:
+ *     u = bits of score_r;  u = (u & 0x80000000) ? ~u : (u | 0x80000000);  key = (~u << 32) | r
+ *   i.e. descending score, ties by position in the NMS output, -0 behind +0, a NaN with the sign bit clear ahead of
+ *   +inf and one with it set behind -inf, as inside an NMS bucket.  kept = min(k, max_det): the first `kept` entries'
+ *   row indices are written to out_idx[seg_begin[s] + 0 .. kept-1], out_counts[s] = kept, out_prefix (int32 [S+1],
+ *   caller's buffer) = the exclusive prefix of the new counts, and out_rows (optional) is regathered densely from
+ *   `rows`, segment after segment.  k <= max_det only reorders.  max_det <= 0 is an argument error; S == 0 and empty
+ *   segments are valid.  mny_nms_merge then works on the reduced lists without change (pass it out_prefix).
+ *   ws: mny_det_topk_ws_bytes() bytes.  One workgroup per segment; more than 4096 kept entries in one segment are
+ *   sorted through global scratch (correct, slow). */
+int mny_yolo_decode_ex(const float* head, const float* anchors_all, const int32_t* mask,
+                       const mny_yolo_head* hp, float obj_thr, float score_thr, int multi_label,
+                       const uint32_t* class_mask, float* rows, int row_stride,
+                       const int32_t* base_counts, int32_t* counts, int32_t* dropped, void* stream);
+int mny_nms_agnostic(const float* rows, const int32_t* seg_begin, const int32_t* seg_count, int S,
+                     int capacity, int max_seg_rows, double thr, int32_t* out_idx, int32_t* out_counts,
+                     float* out_rows, void* ws, void* stream);
+size_t mny_nms_agnostic_ws_bytes(int S, int capacity);
+size_t mny_nms_agnostic_status_offset(int S, int capacity);
+size_t mny_nms_agnostic_prefix_offset(int S, int capacity);
+int mny_det_topk(const float* rows, const int32_t* seg_begin, int S, int capacity, int max_det,
+                 int32_t* out_idx, int32_t* out_counts, float* out_rows, int32_t* out_prefix, void* ws,
+                 void* stream);
+size_t mny_det_topk_ws_bytes(int S, int capacity);
+
 /* ---- fused backward of a depthwise 3x3 stride-1 conv + BN + activation unit ----------------------------
  * One pass over (g, y, x) instead of bn_bwd_apply + dw_bwd_weight + dw_bwd_data (7 tensor passes -> 4): rebuilds
  * dY = ca*g*act'(scale*y+shift) + cb*y + cc in registers from the coefficients `coef` = [3][C] written by

@@ -8,3 +8,4 @@ from . import mbv3  # noqa: F401
 from . import jpeg  # noqa: F401
 from . import anchors  # noqa: F401
 from .jpeg import JpegDecoder  # noqa: F401
+from .postprocess import Detector, PostProcess  # noqa: F401

@@ -202,6 +202,14 @@ _SIGS["mny_det_confusion"] = (c_int, [P] * 9 + [c_int, c_int64, c_int64, c_int, 
 _SIGS["mny_tta_view"] = (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P])
 _SIGS["mny_det_append"] = (c_int, [P, c_int, P, c_int, P, c_int, P, c_int, P])
 _SIGS["mny_nms_merge"] = (c_int, [P, P, P, c_int, P, P, P, c_double, P, P])
+# post-processing options (csrc/postproc.hip; the agnostic NMS is a flag on the bucket kernels of csrc/detect.hip)
+_SIGS["mny_yolo_decode_ex"] = (c_int, [P, P, P, ctypes.POINTER(YoloHead), c_float, c_float, c_int, P, P, c_int, P, P, P, P])
+_SIGS["mny_nms_agnostic"] = (c_int, [P, P, P, c_int, c_int, c_int, c_double, P, P, P, P, P])
+_SIGS["mny_nms_agnostic_ws_bytes"] = (c_size_t, [c_int, c_int])
+_SIGS["mny_nms_agnostic_status_offset"] = (c_size_t, [c_int, c_int])
+_SIGS["mny_nms_agnostic_prefix_offset"] = (c_size_t, [c_int, c_int])
+_SIGS["mny_det_topk_ws_bytes"] = (c_size_t, [c_int, c_int])
+_SIGS["mny_det_topk"] = (c_int, [P, P, c_int, c_int, c_int, P, P, P, P, P, P])
 EXPORTS = tuple(_SIGS)
 
 _lib = None

@@ -13,6 +13,7 @@
 
 #include "common.h"
 #include "iou.h"      // Box, iou_ref: shared with anchors.hip
+#include "detshare.h" // decode_box, the cell decode, desc_key, scan / gather: shared with postproc.hip
 
 namespace mny {
 
@@ -29,17 +30,6 @@ struct LossWs {
     float* scal;         // [16]
     int nb1, nb2;
 };
-
-// decode one cell; order of operations follows yolo_loss.py:89-92,243-247 (Q6, Q13)
-__device__ __forceinline__ Box decode_box(float sx, float sy, float ew, float eh, int gx, int gy, float gf, float aw, float ah) {
-    const float cx = (sx + (float)gx) / gf;
-    const float cy = (sy + (float)gy) / gf;
-    const float w = ew * aw, h = eh * ah;
-    Box b;
-    b.x1 = cx - w / 2; b.y1 = cy - h / 2;
-    b.x2 = w + b.x1; b.y2 = h + b.y1;
-    return b;
-}
 
 // ---- pass 1: one thread per cell: decode, best IoU over the image's GTs, flags ------------------
 __global__ __launch_bounds__(256) void yolo_cells_kernel(const float* __restrict__ head, const float* __restrict__ targets,
@@ -330,14 +320,9 @@ __global__ __launch_bounds__(256) void yolo_decode_kernel(const float* __restric
             const int gx = cell % g, gy = (cell / g) % g, a = cell / (g * g);
             const float* p = head + (((int64_t)n * g + gy) * g + gx) * (A * T) + a * T;
             const int am = mask[a];
-            const Box b = decode_box(sigmoid_ref(p[0]), sigmoid_ref(p[1]), expf(p[2]), expf(p[3]), gx, gy, (float)g,
-                                     anchors[am * 2], anchors[am * 2 + 1]);
-            const float conf = sigmoid_ref(p[4]);
-            float best = -INFINITY; int bi = 0;
-            for (int c = 0; c < hp.C; ++c) {
-                const float s = sigmoid_ref(p[5 + c]);
-                if (s > best) { best = s; bi = c; }
-            }
+            float conf, best;
+            const Box b = decode_cell_box(p, gx, gy, g, anchors[am * 2], anchors[am * 2 + 1], conf);
+            const int bi = decode_cell_best(p, hp.C, best);
             r[0] = b.x1; r[1] = b.y1; r[2] = b.x2; r[3] = b.y2; r[4] = conf; r[5] = best; r[6] = (float)bi;
             keep = conf > val_conf;
         }
@@ -362,12 +347,6 @@ __global__ __launch_bounds__(256) void yolo_decode_kernel(const float* __restric
 // ---- per-class NMS -------------------------------------------------------------------------------
 constexpr int NMS_CAP = 8192;    // max boxes of one (image, class) bucket held in LDS
 
-__device__ __forceinline__ uint32_t desc_key(float s) {       // larger score -> smaller key
-    uint32_t b = __float_as_uint(s);
-    b = (b & 0x80000000u) ? ~b : (b | 0x80000000u);          // ascending-orderable
-    return ~b;
-}
-
 // grid (S, C).  Fills the bucket in original row order (stable), sorts by (score desc, position asc),
 // greedy suppression with block-parallel IoU passes, writes kept row indices to tmp[bucket_base + r].
 // SORT_ONLY (large buckets, see nms_mask_kernel): stops after the sort and writes the sorted boxes / row indices to
@@ -376,7 +355,7 @@ template <bool SORT_ONLY>
 __global__ __launch_bounds__(1024) void nms_bucket_kernel(const float* __restrict__ rows, const int32_t* __restrict__ seg_begin,
                                                           const int32_t* __restrict__ seg_count, int num_classes, double thr, int cap, int32_t* __restrict__ tmp,
                                                           float4* kbox, int32_t* __restrict__ bucket_base, int32_t* __restrict__ kept_count,
-                                                          int32_t* __restrict__ status) {
+                                                          int32_t* __restrict__ status, int agnostic) {
     extern __shared__ __attribute__((aligned(16))) unsigned char nms_smem[];
     unsigned long long* keys = (unsigned long long*)nms_smem;           // [cap2] (score key << 32 | position)
     __shared__ int32_t s_wsum[2][16];
@@ -397,7 +376,7 @@ __global__ __launch_bounds__(1024) void nms_bucket_kernel(const float* __restric
         float score = 0.f;
         if (i < r1) {
             const float* r = rows + (int64_t)i * 7;
-            const float cls = r[6];
+            const float cls = agnostic ? 0.f : r[6];                    // mny_nms_agnostic: column 6 read as 0 (grid (S, 1))
             mine = (cls == cf);
             lower = (cls >= 0.f && cls < cf && cls == floorf(cls));
             if (mine) score = r[5] * r[4];                               // utils/box.py:27
@@ -667,7 +646,7 @@ __global__ __launch_bounds__(1024) void nms_big_bucket_kernel(const float* __res
                                                               const int32_t* __restrict__ seg_count, int num_classes, double thr,
                                                               int32_t* __restrict__ tmp, float4* kbox, const int32_t* __restrict__ bucket_base,
                                                               int32_t* __restrict__ kept_count, unsigned long long* __restrict__ gkeys,
-                                                              int32_t* __restrict__ growidx) {
+                                                              int32_t* __restrict__ growidx, int agnostic) {
     const int s = blockIdx.x, c = blockIdx.y, b = s * num_classes + c;
     const int marker = kept_count[b];
     if (marker >= 0) return;
@@ -689,7 +668,7 @@ __global__ __launch_bounds__(1024) void nms_big_bucket_kernel(const float* __res
         float score = 0.f;
         if (i < r1) {
             const float* r = rows + (int64_t)i * 7;
-            mine = (r[6] == cf);
+            mine = ((agnostic ? 0.f : r[6]) == cf);
             if (mine) score = r[5] * r[4];                               // utils/box.py:27
         }
         const unsigned long long bm = __ballot(mine);
@@ -821,43 +800,6 @@ __global__ __launch_bounds__(256) void nms_compact_kernel(const int32_t* __restr
     if (t0 == 0) out_counts[s] = off - begin;
 }
 
-// single block: exclusive scan of out_counts -> out_prefix[S+1]
-__global__ __launch_bounds__(256) void nms_scan_kernel(const int32_t* __restrict__ counts, int S, int32_t* __restrict__ prefix) {
-    __shared__ int32_t tot[256];
-    __shared__ int32_t carry;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    for (int b0 = 0; b0 < S; b0 += 256) {
-        const int i = b0 + threadIdx.x;
-        const int v = i < S ? counts[i] : 0;
-        tot[threadIdx.x] = v;
-        __syncthreads();
-        for (int d = 1; d < 256; d <<= 1) {
-            const int t = threadIdx.x >= d ? tot[threadIdx.x - d] : 0;
-            __syncthreads();
-            tot[threadIdx.x] += t;
-            __syncthreads();
-        }
-        if (i < S) prefix[i] = carry + tot[threadIdx.x] - v;
-        __syncthreads();
-        if (threadIdx.x == 255) carry += tot[255];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) prefix[S] = carry;
-}
-
-// grid S: gather the kept rows densely, segment after segment
-__global__ __launch_bounds__(256) void nms_gather_kernel(const float* __restrict__ rows, const int32_t* __restrict__ seg_begin,
-                                                         const int32_t* __restrict__ out_idx, const int32_t* __restrict__ out_counts,
-                                                         const int32_t* __restrict__ prefix, float* __restrict__ out_rows) {
-    const int s = blockIdx.x;
-    const int k = out_counts[s], b = seg_begin[s], o = prefix[s];
-    for (int i = blockIdx.y * 256 + threadIdx.x; i < k * 7; i += gridDim.y * 256) {
-        const int r = i / 7, f = i % 7;
-        out_rows[(int64_t)(o + r) * 7 + f] = rows[(int64_t)out_idx[b + r] * 7 + f];
-    }
-}
-
 }  // namespace mny
 
 using namespace mny;
@@ -923,9 +865,9 @@ extern "C" size_t mny_nms_prefix_offset(int S, int capacity, int num_classes) {
     return align256((size_t)(capacity > 0 ? capacity : 1) * 4) + 2 * align256((size_t)S * num_classes * 4);
 }
 
-extern "C" int mny_nms_per_class(const float* rows, const int32_t* seg_begin, const int32_t* seg_count, int S, int capacity,
-                                 int max_seg_rows, int num_classes, double thr, int32_t* out_idx, int32_t* out_counts,
-                                 float* out_rows, void* wsp, void* stream) {
+// the driver of mny_nms_per_class and, with `agnostic` (num_classes == 1, column 6 read as 0), of mny_nms_agnostic
+static int nms_run(const float* rows, const int32_t* seg_begin, const int32_t* seg_count, int S, int capacity, int max_seg_rows, int num_classes,
+                   double thr, int32_t* out_idx, int32_t* out_counts, float* out_rows, void* wsp, void* stream, int agnostic) {
     MNY_REQUIRE(seg_begin && seg_count && out_idx && out_counts && wsp, "nms: null pointer");
     MNY_REQUIRE(S > 0 && capacity >= 0 && num_classes > 0, "nms: bad sizes");
     char* base = (char*)wsp;
@@ -951,19 +893,35 @@ extern "C" int mny_nms_per_class(const float* rows, const int32_t* seg_begin, co
         unsigned long long* mask = (unsigned long long*)((char*)kbox + align256((size_t)(capacity > 0 ? capacity : 1) * 16));
         const int NT = cap / 64;
         hipLaunchKernelGGL(nms_bucket_kernel<true>, dim3(S, num_classes), dim3(1024), lds, st, rows, seg_begin, seg_count, num_classes, thr, cap,
-                           tmp, kbox, bucket_base, kept, status);
+                           tmp, kbox, bucket_base, kept, status, agnostic);
         hipLaunchKernelGGL(nms_mask_kernel, dim3((NT + 1) / 2, S * num_classes), dim3(512), 0, st, kbox, bucket_base, kept, thr, NT, mask);
         hipLaunchKernelGGL(nms_resolve_kernel, dim3(S * num_classes), dim3(256), 0, st, mask, NT, tmp, bucket_base, kept);
     } else
     hipLaunchKernelGGL(nms_bucket_kernel<false>, dim3(S, num_classes), dim3(256), lds, st, rows, seg_begin, seg_count, num_classes, thr, cap, tmp,
-                       kbox, bucket_base, kept, status);
+                       kbox, bucket_base, kept, status, agnostic);
     if (seg_bound > NMS_CAP)                                               // a bucket may exceed the LDS image: those (marked) go through global scratch
         hipLaunchKernelGGL(nms_big_bucket_kernel, dim3(S, num_classes), dim3(1024), 0, st, rows, seg_begin, seg_count, num_classes, thr, tmp, kbox,
-                           bucket_base, kept, gkeys, growidx);
+                           bucket_base, kept, gkeys, growidx, agnostic);
     const int slices = nms_large(S, capacity) ? 64 : 1;                    // few huge segments: spread the copies over more blocks
     hipLaunchKernelGGL(nms_compact_kernel, dim3(S, slices), dim3(256), 0, st, seg_begin, num_classes, tmp, bucket_base, kept, out_idx, out_counts, status);
     hipLaunchKernelGGL(nms_scan_kernel, dim3(1), dim3(256), 0, st, out_counts, S, prefix);
     if (out_rows)
         hipLaunchKernelGGL(nms_gather_kernel, dim3(S, slices), dim3(256), 0, st, rows, seg_begin, out_idx, out_counts, prefix, out_rows);
     return check_launch("nms kernels");
+}
+
+extern "C" int mny_nms_per_class(const float* rows, const int32_t* seg_begin, const int32_t* seg_count, int S, int capacity,
+                                 int max_seg_rows, int num_classes, double thr, int32_t* out_idx, int32_t* out_counts,
+                                 float* out_rows, void* wsp, void* stream) {
+    return nms_run(rows, seg_begin, seg_count, S, capacity, max_seg_rows, num_classes, thr, out_idx, out_counts, out_rows, wsp, stream, 0);
+}
+
+// class-agnostic: one bucket per segment, the workspace of num_classes == 1
+extern "C" size_t mny_nms_agnostic_ws_bytes(int S, int capacity) { return mny_nms_ws_bytes(S, capacity, 1); }
+extern "C" size_t mny_nms_agnostic_status_offset(int S, int capacity) { return mny_nms_status_offset(S, capacity, 1); }
+extern "C" size_t mny_nms_agnostic_prefix_offset(int S, int capacity) { return mny_nms_prefix_offset(S, capacity, 1); }
+
+extern "C" int mny_nms_agnostic(const float* rows, const int32_t* seg_begin, const int32_t* seg_count, int S, int capacity, int max_seg_rows,
+                                double thr, int32_t* out_idx, int32_t* out_counts, float* out_rows, void* wsp, void* stream) {
+    return nms_run(rows, seg_begin, seg_count, S, capacity, max_seg_rows, 1, thr, out_idx, out_counts, out_rows, wsp, stream, 1);
 }

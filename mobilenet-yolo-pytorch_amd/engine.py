@@ -1662,14 +1662,17 @@ class NetPlan:
         t, self.timing = self.timing, None
         return t
 
-    def forward_eval(self, x, val_conf, nms=True):
+    def forward_eval(self, x, val_conf, nms=True, decode=True):
         """`nms=False` leaves the plan's own NMS out (the caller runs one over several plans' candidates, tta.py): rows / cnt1 hold the
-        decoded candidates, out_idx / out_counts / out_rows are not written."""
+        decoded candidates, out_idx / out_counts / out_rows are not written.  `decode=False` leaves the plan's decode out as well (the
+        caller decodes `heads` itself, postprocess.py): only the forward and the seg head's sigmoid run, rows / cnt0 / cnt1 are untouched."""
         x = self._bind(x)
         self.fwd.run()
         for i in range(2):
             self.val_conf[i].value = val_conf[i]
-        if nms:
+        if not decode:
+            self.det.run(self.det_nms + 1)
+        elif nms:
             self.det.run()
         else:
             self.det.run(0, self.det_nms)

@@ -316,6 +316,61 @@ def nms_per_class(rows, seg_begin, seg_count, num_classes, thr=0.45, max_seg_row
     return out_idx, out_counts, out_rows, prefix, status
 
 
+# ---- post-processing options (csrc/postproc.hip) ----------------------------------------------------
+def class_mask(classes, num_classes, device):
+    """The DEVICE uint32 words of mny_yolo_decode_ex's class filter: bit (c & 31) of word (c >> 5) for every c in `classes`."""
+    words = [0] * ((int(num_classes) + 31) // 32)
+    for c in classes:
+        words[c >> 5] |= 1 << (c & 31)
+    return torch.tensor([w - (1 << 32) if w >= (1 << 31) else w for w in words], dtype=torch.int32).to(device)
+
+
+def yolo_decode_ex(head, anchors_all, mask, hp, obj_thr, score_thr=-1.0, multi_label=False, class_mask=None, rows=None, row_stride=None,
+                   base_counts=None):
+    """-> (rows [N,row_stride,7], counts int32 [N], dropped int32 [N]).  row_stride defaults to the worst case of the mode."""
+    cells = hp.A * hp.g * hp.g
+    row_stride = row_stride or cells * (hp.C if multi_label else 1)
+    if rows is None:
+        rows = _new(hp.N, row_stride, 7, like=head)
+    counts = _new(hp.N, like=head, dtype=torch.int32)
+    dropped = _new(hp.N, like=head, dtype=torch.int32)
+    call("mny_yolo_decode_ex", _p(head), _p(anchors_all), _p(mask), ctypes.byref(hp), float(obj_thr), float(score_thr), int(bool(multi_label)),
+         _p(class_mask), _p(rows), int(row_stride), _p(base_counts), _p(counts), _p(dropped), _st())
+    return rows, counts, dropped
+
+
+def nms_agnostic(rows, seg_begin, seg_count, thr=0.45, max_seg_rows=0, gather=True):
+    """Class-agnostic twin of nms_per_class (one bucket per segment; out_rows carries the original rows).  Same return tuple."""
+    capacity = rows.shape[0]
+    S = seg_begin.numel()
+    ws = torch.empty(query("mny_nms_agnostic_ws_bytes", S, capacity), device=seg_begin.device, dtype=torch.uint8)
+    out_idx = torch.empty(max(capacity, 1), device=seg_begin.device, dtype=torch.int32)
+    out_counts = torch.empty(S, device=seg_begin.device, dtype=torch.int32)
+    out_rows = torch.empty(max(capacity, 1), 7, device=seg_begin.device) if gather else None
+    call("mny_nms_agnostic", _p(rows) if capacity else None, _p(seg_begin), _p(seg_count), S, capacity, int(max_seg_rows),
+         float(thr), _p(out_idx), _p(out_counts), _p(out_rows), ctypes.c_void_p(ws.data_ptr()), _st())
+    so = query("mny_nms_agnostic_status_offset", S, capacity)
+    po = query("mny_nms_agnostic_prefix_offset", S, capacity)
+    return out_idx, out_counts, out_rows, ws[po:po + 4 * (S + 1)].view(torch.int32), ws[so:so + 4].view(torch.int32)
+
+
+def det_topk(rows, seg_begin, out_idx, out_counts, out_rows, max_det, ws=None):
+    """Behind nms_per_class / nms_agnostic on the same rows and segments: every segment keeps its `max_det` best entries, in place on
+    out_idx / out_counts / out_rows.  -> the new prefix, int32 [S+1]"""
+    S = seg_begin.numel()
+    capacity = rows.shape[0]
+    assert all(t.dtype == torch.int32 for t in (seg_begin, out_idx, out_counts)) and out_counts.numel() == S
+    assert out_rows is None or (out_rows.dtype == torch.float32 and out_rows.shape[-1] == 7)
+    nbytes = query("mny_det_topk_ws_bytes", S, capacity)
+    if ws is None:
+        ws = torch.empty(nbytes, device=seg_begin.device, dtype=torch.uint8)
+    assert ws.dtype == torch.uint8 and ws.numel() >= nbytes, "det_topk: workspace too small"
+    prefix = torch.empty(S + 1, device=seg_begin.device, dtype=torch.int32)
+    call("mny_det_topk", _p(rows) if capacity else None, _p(seg_begin), S, capacity, int(max_det), _p(out_idx), _p(out_counts), _p(out_rows),
+         _p(prefix), ctypes.c_void_p(ws.data_ptr()), _st())
+    return prefix
+
+
 # ---- test-time augmentation (csrc/tta.hip) ----------------------------------------------------------
 def tta_view(src, Hd, Wd, flip=False, out=None):
     """src [N,C,Hs,Ws] fp32 NCHW -> [N,C,Hd,Wd]: mirrored (flip) then resized bilinearly, half-pixel centres, fp64 arithmetic."""

@@ -8,12 +8,16 @@ every view's pre-NMS candidates are appended per image, un-mirrored, into one jo
 so a change of scale needs no box arithmetic), ONE `mny_nms_per_class` runs over the union and, with `merge`, `mny_nms_merge` replaces
 every kept box by the score-weighted mean of the candidates of its class that overlap it.  One host sync per call (the final counts).
 Opt-in: `model(images)` is untouched, and `TTA(model, views=[(S, False)], merge=False)(x)` equals it bit for bit.
+
+`post=PostProcess(...)` (postprocess.py): every view decodes through `mny_yolo_decode_ex` with the post-processing options, the joint NMS
+is class-aware or class-agnostic at `post.iou_thres` (which then is the merge threshold too, `nms_thr` is not read), and `mny_det_topk`
+caps every image at `post.max_det` before the merge.  `post=None` is the path above.
 """
 import ctypes
 
 import torch
 
-from . import _lib, ops
+from . import _lib, ops, postprocess
 from ._lib import MnyError
 
 
@@ -39,7 +43,7 @@ def default_views(size):
 
 
 class TTA:
-    def __init__(self, model, views, merge=True, nms_thr=0.45):
+    def __init__(self, model, views, merge=True, nms_thr=0.45, post=None):
         try:
             views = [tuple(v) for v in views]
         except TypeError:
@@ -55,6 +59,12 @@ class TTA:
         nms_thr = float(nms_thr)
         if not 0.0 <= nms_thr <= 1.0:
             raise ValueError("nms_thr must lie in [0, 1], got %r" % (nms_thr,))
+        if post is not None:
+            if not isinstance(post, postprocess.PostProcess):
+                raise ValueError("post must be a PostProcess or None, got %r" % (post,))
+            post.check_classes(model.num_classes)
+            nms_thr = post.iou_thres
+        self.post = post
         self.model = model
         self.views = [(int(s), bool(f)) for s, f in views]
         self.merge = bool(merge)
@@ -101,6 +111,8 @@ class TTA:
         if H != W or H != self.views[0][0]:
             raise ValueError("views[0] must be the identity view: the input is %dx%d, views[0] has size %d (square inputs only)"
                              % (H, W, self.views[0][0]))
+        if self.post is not None:
+            return self._call_post(x)
         val_conf = [float(h.val_conf) for h in model.yolo_losses]
         with torch.no_grad():
             plans = model._eval_plans(N, [s for s, _ in self.views], [H, W])
@@ -133,6 +145,64 @@ class TTA:
         dets = list(torch.split(dets, counts))
         if plans[0].seg_head is not None:
             return dets, self._seg[1].cpu().numpy()                             # (output, seg_out) of the identity view, as model(images)
+        return dets
+
+    def _post_buffers(self, N, plans, dev):
+        post, C = self.post, self.model.num_classes
+        strides = [post.stride(p.cap, C) for p in plans]
+        key = (N, tuple(strides), str(dev))
+        b = self._bufs.get(key)
+        if b is None:
+            self._bufs.clear()                                                  # one batch shape resident at a time
+            V = len(plans)
+            b = postprocess.nms_buffers(post, C, N, sum(strides), dev, extra=2 * N * V)
+            b.update({"cap": sum(strides),
+                      "rows": torch.zeros(N, sum(strides), 7, device=dev),
+                      "counts": torch.zeros(N, device=dev, dtype=torch.int32),
+                      "view_rows": [torch.zeros(N, s, 7, device=dev) for s in strides],     # one view's candidates, before they are appended
+                      "cnt0": torch.zeros(N, device=dev, dtype=torch.int32),
+                      "cnt1": torch.zeros(N, device=dev, dtype=torch.int32),
+                      "cmask": ops.class_mask(post.classes, C, dev) if post.classes is not None else None,
+                      "x": {}})
+            self._bufs[key] = b
+        return b
+
+    def _call_post(self, x):
+        """The call with a PostProcess: the same views, appends and merge; decode, NMS and top-k by the options."""
+        model, post = self.model, self.post
+        N, _, H, W = x.shape
+        C = model.num_classes
+        val_conf = [float(h.val_conf) for h in model.yolo_losses]
+        with torch.no_grad():
+            plans = model._eval_plans(N, [s for s, _ in self.views], [H, W])
+            b = self._post_buffers(N, plans, x.device)
+            b["counts"].zero_()
+            out = b["out"]
+            for k, ((size, flip), plan) in enumerate(zip(self.views, plans)):
+                if k not in b["x"] and (size != H or flip):
+                    b["x"][k] = torch.empty(N, 3, size, size, device=x.device)  # resident: the plan reads it through a raw pointer
+                xv = self.view_input(x, k, out=b["x"].get(k))
+                plan.forward_eval(xv, val_conf, decode=False)
+                d0 = N + 1 + 2 * N * k
+                postprocess.decode_plan(plan, post, model, b["view_rows"][k], b["cnt0"], b["cnt1"], out[d0:d0 + N], out[d0 + N:d0 + 2 * N],
+                                        b["cmask"])
+                ops.det_append(b["view_rows"][k], b["cnt1"], b["rows"], b["counts"], flip=flip)
+                if k == 0 and plan.seg_head is not None:
+                    self._seg = (plan.seg_head.to(torch.float32).clone(), plan.seg_eval.clone())
+            postprocess.run_nms(post, C, b["rows"], b["seg_begin"], b["counts"], b["out_idx"], out, b["out_rows"], b["ws"])
+            prefix = postprocess.run_topk(post, b["rows"], b)
+            if self.merge:
+                ops.nms_merge(b["rows"].view(-1, 7), b["seg_begin"], b["counts"], b["out_idx"], out[:N], prefix, b["out_rows"], thr=self.nms_thr)
+            out[N:N + 1].copy_(b["status"])
+            host = out.tolist()                                                 # the one host sync of the call
+            counts, status = host[:N], host[N]
+            postprocess.check_dropped(host[N + 1:], N, " (a TTA view)")
+            if status != 0:
+                raise MnyError("NMS: a bucket of %d boxes exceeded the joint per-image candidate bound" % status)
+            dets = b["out_rows"][:sum(counts)].clone()
+        dets = list(torch.split(dets, counts))
+        if plans[0].seg_head is not None:
+            return dets, self._seg[1].cpu().numpy()
         return dets
 
     def seg_logits(self):
