@@ -1079,6 +1079,134 @@ size_t mny_jpeg_ws_bytes(int n, int64_t coef_elems);
 int mny_jpeg_pixels_batch(const int16_t* coef, const mny_jpeg_item* items, int n, uint8_t* dst,
                           const mny_image_desc* desc, int max_h, int max_w, void* ws, void* stream);
 
+/* ---- baseline JPEG encode: device coefficient stage, host entropy stage (csrc/jpegenc.hip, csrc/jpegenc_host.h) -----------
+ * The way out of the device pipeline (the reference's inference.py:104 writes its result with cv2.imwrite): the decoder's
+ * mirror image, cut at the same place.  Everything per pixel runs on the device and leaves quantised coefficients as int16 in
+ * the layout mny_jpeg_pixels_batch reads (natural order, planes one after another, blocks row-major over the padded grid);
+ * one copy takes them to the host, where Huffman coding, serial and branchy, runs threaded over the images.  All arithmetic
+ * is integer work with arithmetic shifts, and the stream is byte for byte the file libjpeg-turbo writes with its defaults
+ * (Pillow's Image.save(f, "JPEG", quality=Q, subsampling=S), pinned by the tests; tests/jpegenc_ref.py restates both stages
+ * in numpy).  Baseline, 8-bit, three components YCbCr; luma sampling 1x1 (4:4:4), 2x1 (4:2:2) or 2x2 (4:2:0), chroma 1x1; the
+ * typical Huffman tables of Annex K.3, not optimised; quality 1..100; sides up to 16383.
+ *
+ * mny_jpeg_enc_layout (HOST): desc (HOST, [n]) gives h and w of each image (its offset is not read).  items[i] becomes the
+ *   record of image i as the decoder defines it: ncomp 3, hs, vs, the padded block grids bw x bh (whole MCUs), plane_off,
+ *   n_coef, and coef_off = the sum of the n_coef in front of it (multiples of 64), *coef_elems = their total.  q[0] is the
+ *   luminance table, q[1] = q[2] the chrominance table: the tables of Annex K.1 scaled by s = 5000 / Q for Q < 50, else
+ *   200 - 2 Q, each entry clamp((base * s + 50) / 100, 1, 255), integer division.  An image with a side below 1 gets status
+ *   MNY_JPEG_EHEADER, one above 16383 MNY_JPEG_ETOOLARGE, and no coefficients.  MNY_EINVAL: null pointer, n outside 1..4096,
+ *   quality outside 1..100, sampling other than the three above.
+ *
+ * mny_jpeg_coef_batch (DEVICE): src / desc (DEVICE, [n]) = packed uint8 RGB, HWC, offsets multiples of 16; items as
+ *   mny_jpeg_enc_layout wrote them, copied to the device.  One launch.  For component c of size wc x hc (luma: w x h; chroma:
+ *   ceil(w / hs) x ceil(h / vs)) only the blocks of its OWN grid, ceil(wc / 8) x ceil(hc / 8), are computed and written; the
+ *   other blocks of the padded grid are not touched (the host stage codes them without reading them).  Per sample:
+ *     Y  = (19595 R + 38470 G + 7471 B + 32768) >> 16
+ *     Cb = (-11059 R - 21709 G + 32768 B + 8388608 + 32767) >> 16
+ *     Cr = (32768 R - 27439 G - 5329 B + 8388608 + 32767) >> 16
+ *   A full-resolution plane repeats its last column and its last row over its own block grid.  Chroma 2x1, output column x:
+ *   (a + b + (x & 1)) >> 1 over input columns 2x, 2x + 1, a column beyond the image being the last one; rows as for a full
+ *   plane.  Chroma 2x2: (a + b + c + d + 1 + (x & 1)) >> 2 over input columns 2x, 2x + 1 and rows 2y, 2y + 1, a column or row
+ *   beyond the image being the last one, for y < ceil(h / 2); below that the last DOWN-SAMPLED row is repeated (for an even h
+ *   that is not what repeated input rows would give).  Then per 8x8 block: sample - 128, libjpeg's accurate integer forward
+ *   DCT on the rows, then on the columns, with the 13-bit constants of mny_jpeg_pixels_batch.  On (d0..d7):
+ *     t0 = d0 + d7; t7 = d0 - d7; t1 = d1 + d6; t6 = d1 - d6; t2 = d2 + d5; t5 = d2 - d5; t3 = d3 + d4; t4 = d3 - d4;
+ *     t10 = t0 + t3; t13 = t0 - t3; t11 = t1 + t2; t12 = t1 - t2;
+ *     out0 = t10 + t11; out4 = t10 - t11: `<< 2` in the row pass, rounded `>> 2` in the column pass;
+ *     z1 = (t12 + t13) * 4433; out2 = z1 + t13 * 6270; out6 = z1 - t12 * 15137;
+ *     z1 = t4 + t7; z2 = t5 + t6; z3 = t4 + t6; z4 = t5 + t7; z5 = (z3 + z4) * 9633;
+ *     t4 *= 2446; t5 *= 16819; t6 *= 25172; t7 *= 12299; z1 *= -7373; z2 *= -20995; z3 = z3 * -16069 + z5;
+ *     z4 = z4 * -3196 + z5; out7 = t4 + z1 + z3; out5 = t5 + z2 + z4; out3 = t6 + z2 + z3; out1 = t7 + z1 + z4;
+ *     out1, 2, 3, 5, 6, 7 rounded `>> 11` in the row pass and `>> 15` in the column pass; rounding is (x + (1 << (n-1))) >> n.
+ *   Quantise: d = 8 q; c = sign(v) * ((|v| + (d >> 1)) / d).  Every intermediate fits 32 bits.
+ *   The int32 at ws+0 receives 0, or 1 + the lowest index of an item that is not sound: a non-zero status; ncomp other than
+ *   3; sizes, sampling, block grids, plane offsets or n_coef that do not agree with each other; a table entry outside
+ *   1..255; coef_off negative or not a multiple of 8; desc offset negative or not a multiple of 16; desc h, w different
+ *   from the item's or above max_h, max_w.  Such an image is neither read nor written.  As for mny_jpeg_pixels_batch the
+ *   upper bounds (desc offset + 3 h w inside src, coef_off + n_coef inside coef) are the caller's responsibility; the records
+ *   of mny_jpeg_enc_layout satisfy the second for a coef of *coef_elems elements.  n at most 4096; src, items, coef and ws
+ *   16-byte aligned; ws: mny_jpeg_enc_ws_bytes(n) (0 = bad n).  No host sync, no allocation, no atomics; deterministic.
+ *
+ * mny_jpeg_huffman_batch (HOST): coef (coef_elems int16, on the host) and items as above; the stream of image i goes to
+ *   out + out_off[i], at most out_cap[i] bytes, out_len[i] = its length, status[i] = MNY_JPEG_OK; every other status leaves
+ *   out_len[i] = 0.  A slice that is too small gives MNY_JPEG_ECAPACITY (part of the slice may be written, nothing past it),
+ *   as does a negative out_off / out_cap or a coefficient slice outside coef.  A record that is not sound (the rules above)
+ *   gives its own status, MNY_JPEG_ECOLORSPACE, _ESAMPLING, _ETOOLARGE, _EPRECISION (a table entry outside 1..255) or
+ *   _EHEADER.  The stream: SOI; APP0 JFIF 1.01, no density (units 0, 1 x 1), no thumbnail; DQT table 0; DQT table 1; SOF0
+ *   with component ids 1, 2, 3 and tables 0, 1, 1; DHT DC 0, AC 0, DC 1, AC 1; SOS; one interleaved scan; EOI.  A block of an
+ *   MCU outside its component's own grid is coded as all-zero AC with the DC of the block coded just before it in that MCU
+ *   (libjpeg's rule; the transform of padded samples would give other bytes).  DC differences per component; ZRL for runs
+ *   above 15, EOB unless coefficient 63 is non-zero; FF is followed by 00; the last byte is filled with ones.  A DC
+ *   difference beyond 11 bits or an AC coefficient beyond 10 has no baseline code: MNY_JPEG_EHUFFMAN (libjpeg raises an
+ *   error there); pixels never produce one.  n_threads is clamped to 1..16, image i is coded by thread i mod n_threads, so
+ *   the output does not depend on timing; nothing is allocated.  A worst case of 420 bytes per block of the padded grids
+ *   plus 700 for the headers always fits. */
+int mny_jpeg_enc_layout(const mny_image_desc* desc, int n, int quality, int hs, int vs, mny_jpeg_item* items,
+                        int64_t* coef_elems);
+size_t mny_jpeg_enc_ws_bytes(int n);
+int mny_jpeg_coef_batch(const uint8_t* src, const mny_image_desc* desc, const mny_jpeg_item* items, int n, int max_h,
+                        int max_w, int16_t* coef, void* ws, void* stream);
+int mny_jpeg_huffman_batch(const int16_t* coef, int64_t coef_elems, const mny_jpeg_item* items, int n, uint8_t* out,
+                           const int64_t* out_off, const int64_t* out_cap, int64_t* out_len, int32_t* status,
+                           int n_threads);
+
+/* ---- annotation: draw records, then source + box outlines + seg overlay into uint8 images (csrc/viz.hip) ----------------
+ * The reference's inference product (inference.py:58-104) draws the kept boxes on the decoded image and dims the
+ * drivable-area pixels; YOLO trainers write train_batch*.jpg / val_batch*_pred.jpg the same way.  Here both run on the
+ * device, on what the other stages left there, and the result feeds mny_jpeg_coef_batch.  Class names are not drawn (no
+ * font): class identity is by colour.  No host sync, no allocation, no atomics; deterministic; tests/viz_ref.py restates
+ * both entry points in numpy.
+ *
+ * mny_viz_boxes: rows / seg_begin / seg_count / S / capacity as mny_nms_per_class takes them; dims (DEVICE, [S]): h and w of
+ *   the image of segment s (offset is not read).  Record i belongs to row i: nothing is compacted, no count comes back; rows
+ *   outside every segment keep what `out` held.  A segment is clipped to 0 .. capacity.
+ *   mode 0: rows [.,7] = (x1, y1, x2, y2, conf, cls_score, cls), normalised (mny_yolo_decode); drawn iff conf * cls_score >
+ *           thr, one fp32 product, strict (inference.py:83); a NaN fails.
+ *   mode 1: rows [.,5] = (cls, cx, cy, w, h), normalised (mny_yolo_loss's targets); always drawn; x1 = cx - 0.5f * w,
+ *           x2 = cx + 0.5f * w, y1 = cy - 0.5f * h, y2 = cy + 0.5f * h, one fp32 operation each.
+ *   Corners: floor(v * W + 0.5f) for x, floor(v * H + 0.5f) for y, in fp32 without contraction, clamped to +-2^30, then
+ *   ordered: x0 = min, x1 = max, likewise y.  Colour = palette[(int)cls mod P] (DEVICE, P x 3 RGB bytes); t = thickness, 1..8.
+ *   A row that fails the gate, has a NaN corner, or a class that is NaN, negative or >= 2^24 leaves the EMPTY record (t = 0).
+ *
+ * mny_viz_compose: item n -> h x w pixels of 3 bytes (RGB) at dst + dst_offset + y * dst_stride + 3 * x: tiles of one contact
+ *   sheet or separate images; bytes between the rows of an item are not touched.  Three steps, the reference's order:
+ *   1. source.  batch != NULL: fp32 [N,3,H,W], normalised as mny_prep_batch leaves it; channel c of a pixel is
+ *        clamp(floor((x * std3[c] + mean3[c]) * 255 + 0.5), 0, 255): multiply, add, multiply, add in fp32, no contraction; NaN
+ *        gives 0.  mean3 / std3: HOST arrays, read during the call.  Else src + desc (DEVICE, [N]): packed uint8 HWC, copied.
+ *   2. boxes != NULL: the records boxes[seg_begin[n] .. + seg_count[n]) (clipped to 0 .. capacity), in order, later over
+ *        earlier.  Pixel (x, y) takes a record's colour iff t > 0 and
+ *          x0 <= x <= x1 and y0 <= y <= y1 and (x < x0 + t or x > x1 - t or y < y0 + t or y > y1 - t).
+ *        For a box whose two sides are both at least 2 t pixels this is Pillow's ImageDraw.rectangle(outline=, width=t), parts
+ *        outside the image included.  A thinner box is filled by this rule, where Pillow's result differs: for those the
+ *        rule IS the specification.
+ *   3. C > 0: seg + seg_offset = fp32 planes [C,h,w] of the item (mny_seg_upsample).  For class c in order, a pixel with
+ *        p > 0.5f gets v = trunc((float)v * (1.0f - p)) in channel seg_channel[c] (HOST, [C], values 0..2; inference.py:100-
+ *        103 in RGB terms is (1, 0)), a negative product giving 0.  C at most 8.
+ *   The int32 at ws+0 receives 0, or 1 + the lowest index of an item that is not sound: a side outside 1..16383, a negative
+ *   dst_offset (or seg_offset with C > 0), dst_stride below 3 w, sizes that differ from H, W or from desc[n], a negative desc
+ *   offset.  Such an item is neither read nor written.  Upper bounds are the caller's.  ws: mny_viz_ws_bytes(N) (0 = N
+ *   outside 1..4096).  A workgroup owns a 64 x 16 pixel tile; it filters the item's records whose outline meets the tile
+ *   into a list in LDS, 256 records per pass, and its pixels walk only that list. */
+typedef struct mny_viz_box {
+    int32_t x0, y0, x1, y1; /* inclusive pixel corners, ordered */
+    uint8_t rgb[3];
+    uint8_t t;              /* thickness; 0 = empty record */
+} mny_viz_box; /* 20 bytes */
+typedef struct mny_viz_item {
+    int64_t dst_offset; /* bytes from dst to pixel (0,0) */
+    int64_t dst_stride; /* bytes from one row to the next */
+    int64_t seg_offset; /* floats from seg to the item's [C,h,w] planes */
+    int32_t h, w;
+} mny_viz_item; /* 32 bytes */
+int mny_viz_boxes(const float* rows, int mode, const int32_t* seg_begin, const int32_t* seg_count, int S, int capacity,
+                  const mny_image_desc* dims, float thr, const uint8_t* palette, int P, int thickness, mny_viz_box* out,
+                  void* stream);
+size_t mny_viz_ws_bytes(int N);
+int mny_viz_compose(const float* batch, int H, int W, const float* mean3, const float* std3, const uint8_t* src,
+                    const mny_image_desc* desc, const mny_viz_item* items, int N, const mny_viz_box* boxes,
+                    const int32_t* seg_begin, const int32_t* seg_count, int capacity, const float* seg, int C,
+                    const int32_t* seg_channel, uint8_t* dst, void* ws, void* stream);
+
 /* ---- bf16 STORAGE twins (BASELINE config 4: MobileNetV3-YOLO 512x512 bf16) -----------------
  * Every `mny_X_bf16` has the contract of `mny_X` above with ONE difference: the activation-sized tensors (the
  * `void*` parameters: raw conv outputs, materialised sums, gradients wrt activations) are bf16 in HBM.  Kernels

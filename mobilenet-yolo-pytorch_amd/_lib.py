@@ -145,6 +145,10 @@ _SIGS = {
     "mny_jpeg_entropy_batch": (c_int, [P, P, c_int, P, P, P, P, c_int]),
     "mny_jpeg_ws_bytes": (c_size_t, [c_int, c_int64]),
     "mny_jpeg_pixels_batch": (c_int, [P, P, c_int, P, P, c_int, c_int, P, P]),
+    "mny_jpeg_enc_layout": (c_int, [P, c_int, c_int, c_int, c_int, P, P]),
+    "mny_jpeg_enc_ws_bytes": (c_size_t, [c_int]),
+    "mny_jpeg_coef_batch": (c_int, [P, P, P, c_int, c_int, c_int, P, P, P]),
+    "mny_jpeg_huffman_batch": (c_int, [P, c_int64, P, c_int, P, P, P, P, P, c_int]),
     "mny_eval_pack":(c_int, [P, c_int64, P, c_int64, P, P, P, P, P, P, P]),
 }
 # bf16-storage twins (activation tensors bf16, everything else as in the fp32 entry point): identical ctypes signature
@@ -210,6 +214,10 @@ _SIGS["mny_nms_agnostic_status_offset"] = (c_size_t, [c_int, c_int])
 _SIGS["mny_nms_agnostic_prefix_offset"] = (c_size_t, [c_int, c_int])
 _SIGS["mny_det_topk_ws_bytes"] = (c_size_t, [c_int, c_int])
 _SIGS["mny_det_topk"] = (c_int, [P, P, c_int, c_int, c_int, P, P, P, P, P, P])
+# annotation (csrc/viz.hip)
+_SIGS["mny_viz_boxes"] = (c_int, [P, c_int, P, P, c_int, c_int, P, c_float, P, c_int, c_int, P, P])
+_SIGS["mny_viz_ws_bytes"] = (c_size_t, [c_int])
+_SIGS["mny_viz_compose"] = (c_int, [P, c_int, c_int, P, P, P, P, P, c_int, P, P, P, c_int, P, c_int, P, P, P, P])
 EXPORTS = tuple(_SIGS)
 
 _lib = None

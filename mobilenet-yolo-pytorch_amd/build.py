@@ -17,7 +17,7 @@ BASE_FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wall", "
 EXTRA = {"detect.hip": ["-ffp-contract=off"], "evalmap.hip": ["-ffp-contract=off"], "prep.hip": ["-ffp-contract=off"],
          "augment.hip": ["-ffp-contract=off"], "augseq.hip": ["-ffp-contract=off"], "cocoeval.hip": ["-ffp-contract=off"],
          "segeval.hip": ["-ffp-contract=off"], "anchors.hip": ["-ffp-contract=off"], "augwarp.hip": ["-ffp-contract=off"],
-         "detreport.hip": ["-ffp-contract=off"], "tta.hip": ["-ffp-contract=off"], "postproc.hip": ["-ffp-contract=off"]}
+         "detreport.hip": ["-ffp-contract=off"], "tta.hip": ["-ffp-contract=off"], "postproc.hip": ["-ffp-contract=off"], "viz.hip": ["-ffp-contract=off"]}
 
 
 def sources():
@@ -33,7 +33,7 @@ def _stale(target, deps):
 
 def build(force=False, verbose=False):
     os.makedirs(OBJ, exist_ok=True)
-    headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "x6.h"), os.path.join(CSRC, "jpeg_host.h"), os.path.join(CSRC, "pairsort.h"), os.path.join(CSRC, "iou.h"),
+    headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "x6.h"), os.path.join(CSRC, "jpeg_host.h"), os.path.join(CSRC, "jpeg_jobs.h"), os.path.join(CSRC, "jpegenc_host.h"), os.path.join(CSRC, "pairsort.h"), os.path.join(CSRC, "iou.h"),
                os.path.join(CSRC, "boxgeo.h"), os.path.join(CSRC, "detshare.h"),
                os.path.join(HERE, "..", "include", "mnyolo.h")]
     jobs, objs = [], []

@@ -16,6 +16,7 @@
 // augseq.hip does; the grid is capped and strides over it.  Integer arithmetic only; no atomics, no scratch.
 #include "common.h"
 #include "jpeg_host.h"
+#include "jpeg_jobs.h"
 
 static_assert(sizeof(mny_jpeg_item) == 512, "mny_jpeg_item layout (jpeg.py ITEM)");
 static_assert(sizeof(mny_jpeg_info) == 56, "mny_jpeg_info layout (jpeg.py INFO)");
@@ -25,7 +26,7 @@ static_assert(sizeof(mny_image_desc) == 16, "mny_image_desc layout");
 namespace mny {
 namespace {
 
-constexpr int kMaxItems = 4096;
+using namespace jpeg_jobs;
 constexpr int kMaxSide = 16383;
 constexpr size_t kWsHead = 256;          // status word, then the uint8 planes at the coefficients' element offsets
 constexpr int kJobBlocks = 32;           // 8x8 blocks per job of launch (a)
@@ -53,52 +54,6 @@ __device__ bool sound(const mny_jpeg_item* it, const mny_image_desc& d, int max_
     if (d.offset < 0 || (d.offset & 15)) return false;
     if (d.h != h || d.w != w || h > max_h || w > max_w) return false;
     return true;
-}
-
-struct job_lds {
-    uint32_t pref[kMaxItems + 1];
-    uint32_t part[256];
-};
-
-// exclusive prefix sum of count(i) over the items into J.pref; -> the total
-template <typename F>
-__device__ uint32_t build_jobs(job_lds& J, int n, F count) {
-    const int tid = threadIdx.x;
-    const int per = (n + 255) / 256;
-    const int i0 = min(tid * per, n), i1 = min(i0 + per, n);
-    uint32_t local = 0;
-    for (int i = i0; i < i1; ++i) {
-        const uint32_t c = count(i);
-        J.pref[i] = c;
-        local += c;
-    }
-    J.part[tid] = local;
-    __syncthreads();
-    for (int s = 1; s < 256; s <<= 1) {
-        const uint32_t add = tid >= s ? J.part[tid - s] : 0u;
-        __syncthreads();
-        J.part[tid] += add;
-        __syncthreads();
-    }
-    uint32_t run = J.part[tid] - local;
-    for (int i = i0; i < i1; ++i) {
-        const uint32_t c = J.pref[i];
-        J.pref[i] = run;
-        run += c;
-    }
-    const uint32_t total = J.part[255];
-    if (tid == 0) J.pref[n] = total;
-    __syncthreads();
-    return total;
-}
-
-__device__ __forceinline__ int find_item(const job_lds& J, int n, uint32_t job) {   // the last item with pref <= job
-    int lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (J.pref[mid] <= job) lo = mid; else hi = mid;
-    }
-    return lo;
 }
 
 // The 1-D inverse DCT of the header, in place.  The sums run in uint32 so that coefficients no encoder writes wrap

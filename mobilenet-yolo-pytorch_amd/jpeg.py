@@ -11,7 +11,12 @@ call, uses the same libjpeg defaults but is not installed here, so it is unpinne
 (progressive, CMYK, 12-bit, 4:4:0, multi-scan, damaged ones: a non-zero MNY_JPEG_* status per image) go through `fallback`,
 by default Pillow, and land in the same buffer, so the caller sees one uniform result.  The decoder is opt-in:
 `BatchPrep(..., decoder=JpegDecoder())`, `TrainAugment.from_config(cfg, decoder=JpegDecoder())`.  No CPU fallback for the
-supported streams: without libmnyolo.so every call raises MnyError."""
+supported streams: without libmnyolo.so every call raises MnyError.
+
+The way out is the mirror image (`JpegEncoder`, at the end of this file; the reference writes its result with `cv2.imwrite`,
+inference.py:104): everything per pixel on the device into the same int16 coefficient layout (`mny_jpeg_coef_batch`,
+csrc/jpegenc.hip), one copy down, headers and Huffman coding on host threads (`mny_jpeg_huffman_batch`).  The bytes equal the file
+Pillow's `save(f, "JPEG", quality=, subsampling=)` writes; tests pin that too."""
 import ctypes
 import io
 
@@ -216,3 +221,115 @@ class JpegDecoder:
             if v != want:
                 raise RuntimeError("jpeg decode: the device reports image %d as the first one it left alone (misaligned or out-of-bounds "
                                    "descriptor, malformed item record), the host expected %s" % (v - 1, want - 1 if want else "none"))
+
+
+# ---- encode: device coefficients, host entropy coding (include/mnyolo.h "baseline JPEG encode") ----------------------------
+SUBSAMPLING = {"4:4:4": (1, 1), "4:2:2": (2, 1), "4:2:0": (2, 2)}
+HEADER_BYTES, BLOCK_BYTES = 700, 420                # what always fits: the headers, and one block at its worst with every FF stuffed
+
+
+def enc_layout(desc, quality=75, subsampling="4:2:0"):
+    """Host only: `mny_jpeg_enc_layout` -> (items ITEM, coef_elems) for the images of a DESC array."""
+    hs, vs = SUBSAMPLING[subsampling]
+    desc = np.ascontiguousarray(desc, DESC)
+    items = np.zeros(len(desc), ITEM)
+    total = ctypes.c_int64(0)
+    call("mny_jpeg_enc_layout", ctypes.c_void_p(desc.ctypes.data), len(desc), int(quality), hs, vs, ctypes.c_void_p(items.ctypes.data),
+         ctypes.byref(total))
+    return items, int(total.value)
+
+
+def huffman(coef, items, out, out_off, out_cap, threads=8):
+    """Host only: `mny_jpeg_huffman_batch` on numpy buffers (coef int16, items ITEM, out uint8 written in place) -> (lengths, statuses)."""
+    n = len(items)
+    if coef.dtype != np.int16 or items.dtype != ITEM or out.dtype != np.uint8 or not (coef.flags.c_contiguous and items.flags.c_contiguous
+                                                                                     and out.flags.c_contiguous):
+        raise ValueError("coef is a contiguous int16 array, items ITEM records, out a contiguous uint8 array")
+    off = np.ascontiguousarray(out_off, np.int64)
+    cap = np.ascontiguousarray(out_cap, np.int64)
+    if len(off) != n or len(cap) != n or (n and int((off + np.maximum(cap, 0)).max()) > out.size):
+        raise ValueError("the output slices do not fit the buffer")
+    lens = np.zeros(n, np.int64)
+    status = np.zeros(n, np.int32)
+    p = lambda a: ctypes.c_void_p(a.ctypes.data)
+    call("mny_jpeg_huffman_batch", p(coef), coef.size, p(items), n, p(out), p(off), p(cap), p(lens), p(status), int(threads))
+    return lens, status
+
+
+def worst_case(items):
+    """Bytes that hold the stream of every record, whatever its coefficients."""
+    return HEADER_BYTES + BLOCK_BYTES * (items["bw"].astype(np.int64) * items["bh"]).sum(axis=1)
+
+
+def encode_host(coef, items, threads=8, caps=None):
+    """Host only: entropy-code every image of (coef, items) -> (list of bytes, or None where the status is not 0; statuses).
+    `caps`: bytes allowed per image (default: the worst case)."""
+    caps = worst_case(items) if caps is None else np.ascontiguousarray(caps, np.int64)
+    off = np.zeros(len(items), np.int64)
+    off[1:] = np.cumsum(caps)[:-1]
+    out = np.empty(max(int(caps.sum()), 1), np.uint8)
+    lens, status = huffman(coef, items, out, off, caps, threads)
+    return [out[o:o + l].tobytes() if s == OK else None for o, l, s in zip(off, lens, status)], status
+
+
+class JpegEncoder:
+    """enc = JpegEncoder(quality=75, subsampling="4:2:0", device="cuda:0", threads=8)
+       files = enc(buf, desc)
+    buf: packed uint8 RGB images, HWC, on `device` at offsets that are multiples of 16 (what JpegDecoder returns and viz writes);
+    desc: their DESC array (host).  -> one `bytes` per image: the JPEG file, byte for byte what Pillow's
+    `save(f, "JPEG", quality=, subsampling=)` writes for the same pixels.  One launch, one copy of the coefficients to the host,
+    then the threaded host stage."""
+
+    def __init__(self, quality=75, subsampling="4:2:0", device="cuda:0", threads=8):
+        if subsampling not in SUBSAMPLING:
+            raise ValueError("subsampling is one of %s, got %r" % (", ".join(SUBSAMPLING), subsampling))
+        if not 1 <= int(quality) <= 100:
+            raise ValueError("quality is 1..100, got %r" % (quality,))
+        self.quality, self.subsampling = int(quality), subsampling
+        self.device = torch.device(device)
+        self.threads = max(1, min(MAX_THREADS, int(threads)))
+        self.statuses = None                        # per-image MNY_JPEG_* of the last batch (host)
+
+    def coefficients(self, buf, desc, fill=None):
+        """The device stage alone -> (coef int16 on the device, items ITEM on the host, the status word on the device).
+        `fill`: what the coefficient buffer holds before the launch (default: not initialised)."""
+        desc = np.ascontiguousarray(desc, DESC)
+        n = len(desc)
+        if n == 0:
+            raise ValueError("empty batch")
+        if buf.dtype != torch.uint8 or buf.device != self.device or not buf.is_contiguous():
+            raise ValueError("buf is a contiguous uint8 tensor on %s" % self.device)
+        end = desc["offset"] + 3 * desc["h"].astype(np.int64) * desc["w"]
+        if int(desc["offset"].min()) < 0 or int(end.max()) > buf.numel():
+            raise ValueError("an image lies outside buf")
+        items, total = enc_layout(desc, self.quality, self.subsampling)
+        dev = self.device
+        coef = torch.empty(max(total, 64), device=dev, dtype=torch.int16) if fill is None else \
+            torch.full((max(total, 64),), fill, device=dev, dtype=torch.int16)
+        ws = torch.empty(query("mny_jpeg_enc_ws_bytes", n), device=dev, dtype=torch.uint8)
+        i_dev = torch.from_numpy(items.view(np.uint8).copy()).to(dev, non_blocking=True)
+        d_dev = torch.from_numpy(desc.view(np.uint8).copy()).to(dev, non_blocking=True)
+        p = lambda t: ctypes.c_void_p(t.data_ptr())
+        call("mny_jpeg_coef_batch", p(buf), p(d_dev), p(i_dev), n, max(1, int(desc["h"].max())), max(1, int(desc["w"].max())), p(coef), p(ws),
+             ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+        self._keep = (i_dev, d_dev)
+        return coef, items, ws[:4].view(torch.int32)
+
+    def __call__(self, buf, desc):
+        coef, items, word = self.coefficients(buf, desc)
+        host = torch.cat([coef.view(torch.uint8), word.view(torch.uint8)]).cpu().numpy()     # the one copy (and the sync)
+        bad = int(host[-4:].view(np.int32)[0])
+        if bad:
+            raise ValueError("jpeg encode: image %d has a descriptor the device refused (offset not a multiple of 16, size outside "
+                             "1..16383)" % (bad - 1))
+        coef_h = host[:-4].view(np.int16)
+        # the raw size is room enough for all but pathological content; the few images that need more get their worst case
+        files, status = encode_host(coef_h, items, self.threads, np.minimum(worst_case(items), HEADER_BYTES + 3 * items["h"].astype(np.int64) * items["w"]))
+        for i in np.flatnonzero(status == CAPACITY):
+            one, st = encode_host(coef_h, items[i:i + 1], 1)
+            files[i], status[i] = one[0], st[0]
+        self.statuses = status.copy()
+        if (status != OK).any():
+            i = int(np.flatnonzero(status != OK)[0])
+            raise MnyError("jpeg encode: image %d: status %d (%s)" % (i, status[i], STATUS[status[i]]))
+        return files
