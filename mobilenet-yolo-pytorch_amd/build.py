@@ -1,5 +1,5 @@
 """Build libmnyolo.so (gfx950) in-tree with hipcc.  `python -m mobilenet_yolo_pytorch_amd.build`
-or `build()`; objects are rebuilt only when their source (or common.h / mnyolo.h) is newer."""
+or `build()`; objects are rebuilt only when their source (or any csrc/*.h / mnyolo.h) is newer."""
 import os
 import subprocess
 from concurrent.futures import ThreadPoolExecutor
@@ -33,9 +33,7 @@ def _stale(target, deps):
 
 def build(force=False, verbose=False):
     os.makedirs(OBJ, exist_ok=True)
-    headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "x6.h"), os.path.join(CSRC, "jpeg_host.h"), os.path.join(CSRC, "jpeg_jobs.h"), os.path.join(CSRC, "jpegenc_host.h"), os.path.join(CSRC, "pairsort.h"), os.path.join(CSRC, "iou.h"),
-               os.path.join(CSRC, "boxgeo.h"), os.path.join(CSRC, "detshare.h"),
-               os.path.join(HERE, "..", "include", "mnyolo.h")]
+    headers = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join(HERE, "..", "include", "mnyolo.h")]
     jobs, objs = [], []
     for src in sources():
         s = os.path.join(CSRC, src)
@@ -50,7 +48,7 @@ def build(force=False, verbose=False):
         subprocess.check_call(cmd)
 
     if jobs:
-        with ThreadPoolExecutor(max_workers=min(4, len(jobs))) as ex:
+        with ThreadPoolExecutor(max_workers=min(8, len(jobs))) as ex:
             list(ex.map(run, jobs))
     if jobs or force or _stale(LIB, objs):
         run([HIPCC, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-fvisibility=hidden", "-Wl,--exclude-libs,ALL", "-o", LIB] + objs)

@@ -24,7 +24,7 @@
 // disjoint register live sets).  Measured (LAB_NOTES.md R4.1): fp32 MFMA time and vector-ALU time ADD on this part, so these kernels
 // are bound by total instruction issue, not by a pipe or by HBM; a first generation on the vector ALU alone (X rows broadcast from LDS,
 // 4 x K weights per thread in registers) ran LDS- and ALU-bound together at half the rate and is gone.
-#include "common.h"
+#include "pwgemm.h"
 
 namespace mny {
 

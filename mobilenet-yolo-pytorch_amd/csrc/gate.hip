@@ -28,7 +28,7 @@
 // tensors are NOT rounded through storage any more (oracle/bf16_storage.py models exactly that).
 #include <stdlib.h>
 
-#include "common.h"
+#include "pwgemm.h"
 #include "x6.h"
 
 namespace mny {

@@ -3,7 +3,7 @@
 // These are the "expand" convs of the early inverted-residual blocks (16->96, 24->144, 32->192: mobilenetv2.py:61) and the data
 // gradients of the matching "project" convs (contraction over 16 / 24 / 32 output channels: autograd of mobilenetv2.py:69,83), all
 // at the largest feature maps.  They carry 8-16 flops per output byte: pure HBM streams.  On the matrix-core tile kernel
-// (pwgemm.hip) they reached 2.8-4.7 of the 5.5-6 TB/s a flat copy gets on this part (profiles/r02_kernels_time_and_hbm.md):
+// (pwnt_kernel.h) they reached 2.8-4.7 of the 5.5-6 TB/s a flat copy gets on this part (profiles/r02_kernels_time_and_hbm.md):
 // a 16/24/32-deep reduction is one or two MFMA k-steps, so the tile machinery (LDS ring, barriers per k-step, DPP transposes in
 // the epilogue, 32-column padding of 144 = 4.5 tiles) is all overhead.  Here instead:
 //   * a thread owns 4 output columns and keeps their 4 x K weights in registers for the whole launch (persistent blocks);
@@ -13,8 +13,8 @@
 //   * 2K packed FMAs (v_pk_fma_f32) per thread-row, one 16-B streaming store: ~20 instructions per output quad, below what the
 //     store stream needs to stay at HBM rate;
 //   * the column statistics (forward: sum / sum of squares of the stored outputs; RED: the BN-backward sums of the unit the
-//     gradient belongs to, pwgemm.hip RED = 1 / 2 semantics) are per-thread running sums, folded once at the end.
-#include "common.h"
+//     gradient belongs to, pwnt_kernel.h RED = 1 / 2 semantics) are per-thread running sums, folded once at the end.
+#include "pwgemm.h"
 
 #include <type_traits>
 

@@ -11,7 +11,7 @@
 // side (TB or TA blocks of 32) x a 64-column slice of the wide side; its four waves' accumulators are combined through LDS once, at
 // the end, into one partial row of [splits][N][K] (the layout of the other weight-gradient kernels; combined by the same reducers).
 // fp32 storage, M % 16 == 0; no loop branch around a load, no store in the loop.
-#include "common.h"
+#include "pwgemm.h"
 #include "x6.h"
 
 namespace mny {

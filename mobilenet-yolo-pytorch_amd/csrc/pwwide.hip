@@ -1,7 +1,7 @@
 // Pointwise conv with a SHORT reduction feeding a WIDE output (K = 64..96 input channels, N >= K outputs: the expand convs of
 // the 14x14 / 22x22 bottlenecks and the data gradients of their project convs) — barrier-free kernel on the bf16 matrix cores.
 //
-// Why a third GEMM kernel.  On these shapes the LDS-DMA ring kernel (pwgemm.hip) runs at 2.7-3.1 TB/s, half of what the
+// Why a third GEMM kernel.  On these shapes the LDS-DMA ring kernel (pwnt_kernel.h) runs at 2.7-3.1 TB/s, half of what the
 // tensors cost to stream: a tile is only 4-6 k-stages deep, so a workgroup meets a barrier + a DMA wait every ~200 matrix
 // cycles and, in the reduction-epilogue form, adds a load round trip per column block (tools/ab_lib_detail.sh).  Here nothing
 // in the loop is shared between waves:
@@ -14,12 +14,12 @@
 //   * column blocks are the OUTER loop of a tile (u: 32 columns, 6*KS MFMAs, then their epilogue), so stores, epilogue VALU work
 //     and the next block's matrix work interleave, and the reduction epilogue's operand (the fed unit's raw output, MFMA
 //     layout) is requested one block ahead;
-//   * epilogue = the DPP quad transpose of pwgemm.hip (lane jq of a quad: one row, 4 consecutive columns, 16-B streaming store).
+//   * epilogue = the DPP quad transpose of pwnt_kernel.h (lane jq of a quad: one row, 4 consecutive columns, 16-B streaming store).
 // Partial rows ([gx][2][N]) have the layout of the other pointwise kernels.  fp32 storage only.
 #include <mutex>
 #include <vector>
 
-#include "common.h"
+#include "pwgemm.h"
 #include "x6.h"
 
 namespace mny {

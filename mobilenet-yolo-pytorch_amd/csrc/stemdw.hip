@@ -18,7 +18,7 @@
 // three image rows of its patches go to LDS and the matrix cores take the bilinear sums: the loaded dword of the image IS both operands
 // of the patch second-moment product (v_mfma_f32_16x16x4_f32: A[i][k] = P[k][i], B[k][j] = P[k][j], k = the pixel).
 // fp32 storage, Cout = 32, activations of the ReLU / ReLU6 / leaky family (no h-swish: MobileNetV3's stem keeps the unfused kernels).
-#include "common.h"
+#include "pwgemm.h"
 
 namespace mny {
 

@@ -1,7 +1,9 @@
 #!/bin/bash
-# usage: bash tools/ab/build_variant.sh NAME [extra hipcc flags...]  -> tools/ab/lib_NAME.so = the in-tree objects with pwgemm.hip rebuilt under the flags
+# usage: bash tools/ab/build_variant.sh NAME SOURCE [extra hipcc flags...]  -> tools/ab/lib_NAME.so = the in-tree objects with csrc/SOURCE.hip
+# (pwgemm, pwntred, ...) rebuilt under the flags
 set -e
-R=/root/repo; C=$R/mobilenet-yolo-pytorch_amd/csrc; N=$1; shift
-mkdir -p /tmp/hz
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-function "$@" -c $C/pwgemm.hip -o /tmp/hz/pwgemm_$N.o 2>&1 | grep -E "error" || true
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $R/tools/ab/lib_$N.so /tmp/hz/pwgemm_$N.o $(ls $C/_obj/*.o | grep -v pwgemm.o)
+R=$(cd "$(dirname "$0")/../.." && pwd); C=$R/mobilenet-yolo-pytorch_amd/csrc; N=$1; S=${2%.hip}; shift 2
+T=$(mktemp -d); trap 'rm -rf "$T"' EXIT
+HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
+$HIPCC --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-function "$@" -c $C/$S.hip -o $T/$S.o      # (set -e: a failed compile stops here)
+$HIPCC --offload-arch=gfx950 -shared -fPIC -o $R/tools/ab/lib_$N.so $T/$S.o $(ls $C/_obj/*.o | grep -v "/$S\.o$")

@@ -57,6 +57,11 @@ def listings(co):
         elif pc and re.match(r"s_addc_u32 %s, %s, (0x[0-9a-f]+|-?\d+)$" % (pc[1], pc[1]), ins):
             ins, pc = "s_addc_u32 %s, %s, <pcrel>" % (pc[1], pc[1]), None
         cur.append(ins)
+    # a function ends at s_endpgm / its last branch; the alignment padding behind it depends on what FOLLOWS it in the object, not on the function
+    # (KEEP_PADDING=1 compares it too: shows which functions differ in nothing else)
+    for body in out.values() if not os.environ.get("KEEP_PADDING") else ():
+        while body and body[-1] in ("s_nop 0", "...", "s_code_end"):
+            body.pop()
     return out
 
 
