@@ -103,7 +103,8 @@ int mny_pw_fwd(const float* x, const float* in_scale, const float* in_shift, int
                int64_t M, int K, int Nc, void* stream);
 int mny_pw_stat_parts(int64_t M, int K, int Nc);
 /* dw[Nc,K] = dy[M,Nc]^T * act_in(x)[M,K]; dbias[Nc] (optional) = column sums of dy.
- * ws holds mny_pw_wgrad_ws_floats() floats. */
+ * ws holds mny_pw_wgrad_ws_floats() floats (the same query serves mny_pw_wgrad_bf16: it covers the partial rows of
+ * either storage type, so at a 96-wide side, where the bf16 plan has up to twice the splits, the fp32 caller's workspace is sized for the bf16 plan too). */
 int mny_pw_wgrad(const float* x, const float* in_scale, const float* in_shift, int in_act,
                  const float* dy, float* dw, float* dbias, float* ws,
                  int64_t M, int K, int Nc, void* stream);
@@ -584,6 +585,14 @@ int mny_pw_route(int op, int bf16, int64_t M, int K, int Nc);   /* the family of
 /* the family the LAST pointwise-conv call of the calling thread actually took (every launcher records the route it acted on; -1 before
  * the first call).  engine.py records it for every call of a plan's first replay: NetPlan.kernel_routes() reports what ran. */
 int mny_pw_last_route(void);
+/* Which KERNEL a weight-gradient call launches (pure host query), from the decision the launcher itself acts on:
+ * template * 1000 + MODE * 100 + TI * 10 + TJ, template 0 = register-staged pw_wgrad_kernel, 1 = LDS-DMA fp32 MFMA, 2 = LDS-DMA six-product
+ * form, 3 = LDS-DMA bf16 storage, 5 = the stream kernel (tile digits 0).  has_view: in_scale / in_shift are passed; bias_grad: dbias is.
+ * The six-product form exists for five MODE 0 tiles; a call of the MNY_ROUTE_DMA_X6 family on any other tile (every MODE 1 plan, e.g.
+ * K 96 N 576) launches the fp32-MFMA kernel of that tile and reports template 1 here while its family stays MNY_ROUTE_DMA_X6.
+ * MNY_EINVAL on an empty problem.  mny_pw_wgrad_last_kernel: the code of the calling thread's last mny_pw_wgrad[_bf16] call (-1 before). */
+int mny_pw_wgrad_kernel(int bf16, int64_t M, int K, int Nc, int in_act, int has_view, int bias_grad);
+int mny_pw_wgrad_last_kernel(void);
 
 /* ---- evaluation consumer: VOC07 11-point mAP on the device -----------------------------
  * Replaces utils/eval_mAP.py:134-187 (calculate_mAP), :69-132 (eval_class_ap), :8-65

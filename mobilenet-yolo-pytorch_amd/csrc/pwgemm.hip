@@ -981,8 +981,14 @@ static WgKernel wg_bf16_kernel(int mode, int TI, int TJ, int XF) {
     }
 }
 
+// the tiles the six-product form is compiled for (the cases of wg_dma_kernel below); every other tile of a six-product route runs the fp32 MFMA
+static bool wg_has_x6(int mode, int TI, int TJ) {
+    const int t = TI * 10 + TJ;
+    return mode == 0 && (t == 11 || t == 12 || t == 21 || t == 22 || t == 24);
+}
+
 static WgKernel wg_dma_kernel(int mode, int TI, int TJ, int x6 = 0) {
-    if (x6 && mode == 0) switch (TI * 10 + TJ) {
+    if (x6 && wg_has_x6(mode, TI, TJ)) switch (TI * 10 + TJ) {
         case 11: return (WgKernel)pw_wgrad_dma_kernel<0, 1, 1, 1>; case 12: return (WgKernel)pw_wgrad_dma_kernel<0, 1, 2, 1>;
         case 21: return (WgKernel)pw_wgrad_dma_kernel<0, 2, 1, 1>; case 22: return (WgKernel)pw_wgrad_dma_kernel<0, 2, 2, 1>;
         case 24: return (WgKernel)pw_wgrad_dma_kernel<0, 2, 4, 1>;
@@ -1912,6 +1918,7 @@ int pw_bnbwd_finalize_launch(const float* partials, int nparts, float* red, cons
 
 using namespace mny;
 static thread_local int g_pw_route = -1;        // kernel family of this thread's last pointwise-conv call (mny_pw_last_route below)
+static thread_local int g_wg_kernel = -1;       // kernel code of this thread's last weight-gradient call (mny_pw_wgrad_last_kernel below)
 
 // ---- which kernel a pointwise-conv call takes ------------------------------------------------------------------------------------------
 // One route function per operation: the complete description of a call in, the decision out.  The launchers act on it, and every *_parts /
@@ -1929,6 +1936,8 @@ struct PwRoute {
     Nt2Plan p2{};                       // LDS-DMA families (and the wide family's last rows)
     size_t lds = 0;                     //   their dynamic LDS
     WgPlan wg{};                        // weight gradient, tile kernels
+    int wg_xf = 0;                      //   the XF of the bf16 LDS-DMA kernel: 0 = no view, 1 = linear / clamp view, 2 = h-swish view
+    int wg_kernel = MNY_EINVAL;         //   the kernel launched: template * 1000 + MODE * 100 + TI * 10 + TJ (mny_pw_wgrad_kernel)
 };
 
 // Pre-cut weight planes pay where the matrix pipe is the bound.  Round 2: a stage of B grew from 64 to 96 bytes per row, which cost the mid-size
@@ -2056,12 +2065,13 @@ static PwRoute pw_lr_fix_route(int64_t M, int K, int r_act, bool red, bool view)
 }
 
 // weight gradient (mny_pw_wgrad, _bf16); parts = the splits of the partial rows [splits][Nc][K]
-static PwRoute pw_wgrad_route(int bf, int64_t M, int K, int Nc, int in_act, bool bias_grad) {
+static PwRoute pw_wgrad_route(int bf, int64_t M, int K, int Nc, int in_act, bool bias_grad, bool view) {      // view: in_scale / in_shift are passed
     PwRoute r;
     if (M <= 0 || K <= 0 || Nc <= 0) { r.why = "empty problem"; return r; }
     if (!bf && pw_wgs_ok(M, K, Nc) && !bias_grad) {        // narrow-sided shape: barrier-free stream kernel (pwwgs.hip)
         r.family = MNY_ROUTE_WGRAD_STREAM;
         r.parts = pw_wgs_splits(M, K, Nc);
+        r.wg_kernel = 5000;
         return r;
     }
     // the LDS-DMA kernels read raw 16-B chunks: aligned rows only; the fp32 one has no h-swish view
@@ -2071,6 +2081,13 @@ static PwRoute pw_wgrad_route(int bf, int64_t M, int K, int Nc, int in_act, bool
     r.family = !dma ? MNY_ROUTE_TILE_V1 : r.x6 ? MNY_ROUTE_DMA_X6 : MNY_ROUTE_DMA_F32;
     r.wg = wg_plan(M, K, Nc, bf, !bf && dma);
     r.parts = r.wg.splits;
+    r.wg_xf = (!view && in_act == MNY_ACT_NONE) ? 0 : (in_act == MNY_ACT_HSWISH ? 2 : 1);
+    // The kernel template.  The six-product form is compiled for five MODE 0 tiles only: a six-product route whose plan is MODE 1 (K 96, N 576)
+    // or another MODE 0 tile (!wg_has_x6) runs the plain fp32-MFMA kernel of that tile: wg_dma_kernel falls through to its second table.  That is kept as it
+    // is.  The family stays MNY_ROUTE_DMA_X6 — it names the rule the shape fell under —, the kernel code says template 1: what is launched.
+    const int tile = r.wg.mode * 100 + r.wg.TI * 10 + r.wg.TJ;
+    const int tmpl = !dma ? 0 : bf ? 3 : (r.x6 && wg_has_x6(r.wg.mode, r.wg.TI, r.wg.TJ)) ? 2 : 1;
+    r.wg_kernel = tmpl * 1000 + tile;
     return r;
 }
 
@@ -2267,17 +2284,26 @@ extern "C" int mny_pw_route(int op, int bf16, int64_t M, int K, int Nc) {
     const int bf = bf16 ? 1 : 0;
     if (op == 0) return pw_fwd_route(bf, M, K, Nc, MNY_ACT_NONE, false, false, false, false).family;
     if (op == 1) return pw_dgrad_bnred_route(bf, M, K, Nc, MNY_ACT_NONE, false, false).family;
-    return pw_wgrad_route(bf, M, K, Nc, MNY_ACT_NONE, false).family;
+    return pw_wgrad_route(bf, M, K, Nc, MNY_ACT_NONE, false, false).family;
 }
 
-// room for whichever kernel the call takes: with a bias gradient the narrow-sided shapes stay off the stream kernel
+// room for whichever kernel the call takes: with a bias gradient the narrow-sided shapes stay off the stream kernel, and the bf16 entry point (which
+// has no query of its own) plans a 96-wide side on the 2x2-wave tiles with 16-row chunks: up to twice the splits of the fp32 plan (K 96, N 200).
+// An fp32 caller at such a shape pays for the bf16 plan's rows too (memory only).
 extern "C" size_t mny_pw_wgrad_ws_floats(int64_t M, int K, int Nc) {
     if (M <= 0 || K <= 0 || Nc <= 0) return 0;
-    const int a = pw_wgrad_route(0, M, K, Nc, MNY_ACT_NONE, false).parts, b = pw_wgrad_route(0, M, K, Nc, MNY_ACT_NONE, true).parts;
-    return (size_t)(a > b ? a : b) * Nc * K + (size_t)colsum_parts(M) * Nc;
+    int parts = pw_wgrad_route(0, M, K, Nc, MNY_ACT_NONE, false, false).parts;
+    for (const int p : {pw_wgrad_route(0, M, K, Nc, MNY_ACT_NONE, true, false).parts, pw_wgrad_route(1, M, K, Nc, MNY_ACT_NONE, false, false).parts})
+        if (p > parts) parts = p;
+    return (size_t)parts * Nc * K + (size_t)colsum_parts(M) * Nc;
 }
-extern "C" int mny_pw_wgrad_splits(int64_t M, int K, int Nc) { return pw_wgrad_route(0, M, K, Nc, MNY_ACT_NONE, false).parts; }
-extern "C" int mny_pw_wgrad_splits_bf16(int64_t M, int K, int Nc) { return pw_wgrad_route(1, M, K, Nc, MNY_ACT_NONE, false).parts; }
+extern "C" int mny_pw_wgrad_splits(int64_t M, int K, int Nc) { return pw_wgrad_route(0, M, K, Nc, MNY_ACT_NONE, false, false).parts; }
+extern "C" int mny_pw_wgrad_splits_bf16(int64_t M, int K, int Nc) { return pw_wgrad_route(1, M, K, Nc, MNY_ACT_NONE, false, false).parts; }
+// which kernel a weight-gradient call launches, and which one this thread's last call did launch: both read the route's wg_kernel
+extern "C" int mny_pw_wgrad_kernel(int bf16, int64_t M, int K, int Nc, int in_act, int has_view, int bias_grad) {
+    return pw_wgrad_route(bf16 ? 1 : 0, M, K, Nc, in_act, bias_grad != 0, has_view != 0).wg_kernel;
+}
+extern "C" int mny_pw_wgrad_last_kernel(void) { return g_wg_kernel; }
 
 template <typename T>
 static int pw_wgrad_impl(const T* x, const float* in_scale, const float* in_shift, int in_act, const T* dy,
@@ -2285,9 +2311,10 @@ static int pw_wgrad_impl(const T* x, const float* in_scale, const float* in_shif
     MNY_REQUIRE(x && dy && ws, "pw_wgrad: null pointer");
     MNY_REQUIRE(dw || !dbias, "pw_wgrad: a deferred combine (dw == NULL) cannot carry a bias gradient");
     constexpr bool is_f32 = sizeof(T) == 4;
-    const PwRoute r = pw_wgrad_route(!is_f32, M, K, Nc, in_act, dbias != nullptr);
+    const PwRoute r = pw_wgrad_route(!is_f32, M, K, Nc, in_act, dbias != nullptr, in_scale != nullptr);
     MNY_REQUIRE(!r.why, "pw_wgrad: %s", r.why);
     g_pw_route = r.family;
+    g_wg_kernel = r.wg_kernel;
     hipStream_t st = (hipStream_t)stream;
     if (r.family == MNY_ROUTE_WGRAD_STREAM) {              // partial rows [r.parts][Nc][K]
         int rc = pw_wgs_launch((const float*)x, in_scale, in_shift, in_act, (const float*)dy, ws, M, K, Nc, st);
@@ -2300,8 +2327,8 @@ static int pw_wgrad_impl(const T* x, const float* in_scale, const float* in_shif
     WgradArgs a{x, in_scale, in_shift, in_act, dy, ws, M, K, Nc, pl.rows_per_block, 0, pl.gy, pl.splits};
     dim3 grid(pl.gx, pl.gy, pl.splits), block(256);
     if (r.family != MNY_ROUTE_TILE_V1) {                   // LDS-DMA kernels
-        const int XF = (in_scale == nullptr && in_act == MNY_ACT_NONE) ? 0 : (in_act == MNY_ACT_HSWISH ? 2 : 1);
-        const WgKernel dk = is_f32 ? wg_dma_kernel(pl.mode, pl.TI, pl.TJ, r.x6) : wg_bf16_kernel(pl.mode, pl.TI, pl.TJ, XF);
+        const int tmpl = r.wg_kernel / 1000;                // 1: fp32 MFMA, 2: six-product form, 3: bf16 storage
+        const WgKernel dk = tmpl == 3 ? wg_bf16_kernel(pl.mode, pl.TI, pl.TJ, r.wg_xf) : wg_dma_kernel(pl.mode, pl.TI, pl.TJ, tmpl == 2);
         if (!dk) {
             set_error("pw_wgrad: no kernel for mode %d tile %dx%d", pl.mode, pl.TI, pl.TJ); return MNY_EUNSUPPORTED;
         }
