@@ -16,7 +16,7 @@
 //   backward  exdw_bwd1v2_s2 : Y again; dZ rebuilt from (G_z, Z) -> dW_dw, G_a = dw^T(dZ), dz = G_a * relu6'(z) -> BN sums of the expand
 //                              unit, P1 = dz^T X, Gram = X^T X, colsum(X), and dz (ca o W)^T -> dX (ca = gamma * invstd is known
 //                              BEFORE the BN-backward sums)                                                           (reads X, G_z, Z; writes dX)
-//             finalize       : the expand unit's dgamma / dbeta / dW, Q = W^T diag(cb) W, bias = cc . W               (pwgemm.hip, fp64)
+//             finalize       : the expand unit's dgamma / dbeta / dW, Q = W^T diag(cb) W, bias = cc . W               (pwbnbwd.hip, fp64)
 //             exdw_dxfix     : dX += X Q^T + bias (+ addend); optionally the BN-backward sums of the unit in front     (thin tensors only)
 //
 // 512-thread workgroups split into PRODUCER waves (matrix cores) and CONSUMER waves (stencil threads: 4 channels x one column, lanes =
@@ -1044,7 +1044,7 @@ static int ex_bwd1v2_launch(const ExBwdArgs& a, bool xf, int grid, hipStream_t s
 }
 
 // ---- the thin remainder of the data gradient: dx += view(X) Q^T + bias (+ addend) -------------------------------------------------
-// Q[K][K] = W^T diag(cb) W and bias[K] = cc . W depend on the BN-backward sums (fp64 finalize, pwgemm.hip); X and dx are K channels wide.
+// Q[K][K] = W^T diag(cb) W and bias[K] = cc . W depend on the BN-backward sums (fp64 finalize, pwbnbwd.hip); X and dx are K channels wide.
 // Thread = one pixel x 4 output channels; the pixel's K inputs arrive as 16-B loads shared by its K/4 threads (adjacent lanes).
 // RED: x is the raw output of a conv+BN(+act) unit consumed only here, so the finished dx IS that unit's complete output gradient: its
 // BN-backward sums (sum dz, sum dz * yhat; mny_bn_bwd_reduce's arithmetic) leave with it as partial rows [gridDim.x][2][K] and the

@@ -892,7 +892,7 @@ int pwt_launch(const void* x, const float* xs, const float* xb, int xact, const 
 }
 
 // ---- thin expand unit backward (conv K -> N + BN + ReLU-family activation), bf16 storage, on the same machinery ------------------------
-// mny_pw_bnbwd's algebra (pwgemm.hip): dW = ca o (dz^T B) + cb o (W B^T B) + cc x colsum(B), dX = dz (ca o W) + B Q + bias with dz = G * act'(BN(Y)),
+// mny_pw_bnbwd's algebra (pwbnbwd.hip): dW = ca o (dz^T B) + cb o (W B^T B) + cc x colsum(B), dX = dz (ca o W) + B Q + bias with dz = G * act'(BN(Y)),
 // B = the activated input view.  Its bf16 instantiation keeps the fp32 32x32x2 matrix instructions and reads LDS one element per lane and
 // instruction: element-rate-bound at 2.9 TB/s on 16 -> 64 @256x256 (0.41 + 0.24 ms).  Here
 //   stage A (pwe_sums_kernel): a wave per 16 pixels loads G, Y (N wide) and X (K thin) in the accumulator layout, forms dz and B per lane, keeps the
@@ -912,7 +912,7 @@ struct PweArgs {
 };
 // Stage A: BW waves per workgroup park 16 BW pixels and share the tiles.  Measured (whole unit, same box): 16 -> 64 @256x256 8 waves 0.701 ms, 4 waves
 // 0.592 (two workgroups per CU: one's barriers overlap the other's loads), a barrier-free variant (every wave transposes its own 16 pixels, 32-deep
-// matrix instruction half empty) 0.628, the fp32-MFMA kernel of pwgemm.hip 0.779; 24 -> 72 @128x128: 8 waves 0.220, 4 waves 0.272, pwgemm.hip 0.256.
+// matrix instruction half empty) 0.628, the fp32-MFMA kernel of pwbnbwd.hip 0.779; 24 -> 72 @128x128: 8 waves 0.220, 4 waves 0.272, pwbnbwd.hip 0.256.
 template <int KT, int NT, int BW>
 struct PweLds {
     static constexpr int kPweBW = BW, kPwePitch = 16 * BW + 8;
@@ -1182,7 +1182,7 @@ static int pwe_launch_b(const PweArgs& a, int NT, int grid, hipStream_t st) {
     else hipLaunchKernelGGL((pwe_dgrad_kernel<KT, 5>), dim3(grid), dim3(256), 0, st, a);
     return check_launch("pwe_dgrad_kernel");
 }
-// the whole unit: stage A -> combine + fp64 finalize (pw_bnbwd_finalize_launch, pwgemm.hip) -> stage B.  Same arguments as mny_pw_bnbwd_bf16.
+// the whole unit: stage A -> combine + fp64 finalize (pw_bnbwd_finalize_launch, pwbnbwd.hip) -> stage B.  Same arguments as mny_pw_bnbwd_bf16.
 int pwe_launch(const void* g, const void* y, const float* scale, const float* shift, int act, const float* mean, const float* invstd, const float* gamma,
                const void* x, const float* in_scale, const float* in_shift, int in_act, const float* w, const void* addend, void* dx, float* dw,
                float* dgamma, float* dbeta, float* ws, int64_t M, int K, int Nc, hipStream_t st) {

@@ -13,7 +13,7 @@
 //     mny_lr_prep   : after mny_bn_bwd_finalize: Q (symmetric: it is its own NT operand) and r, on the fp32 matrix cores
 //     mny_pw_lr_fix : dX += X Q + r  (X through its linear view in the GEMM's A-fragment read; + the BN-backward sums of the unit in front)   [pwgemm.hip]
 //     mny_lr_wfix   : dW += cb o (W G) + cc (x) s   in place, after the partial combine
-// Same algebra as the thin expand units' mny_pw_bnbwd (pw_bnbwd_finalize_kernel), for K = 64 ... 320 where its one-workgroup finalize and
+// Same algebra as the thin expand units' mny_pw_bnbwd (pw_bnbwd_finalize_kernel, pwbnbwd.hip), for K = 64 ... 320 where its one-workgroup finalize and
 // K <= 32 stream kernels do not reach.
 #include "common.h"
 #include "x6.h"

@@ -4,6 +4,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "dma_zero.h"      // mny_zero16: the DMA source for B chunks past K
 #include "x6.h"
 
 namespace mny {
@@ -13,7 +14,7 @@ constexpr int BM = 128;
 // ------------------------------------------------------------------------------------------------
 // NT GEMM v2: LDS-DMA pipeline.
 //
-// The register-staged kernel (pw_gemm_nt_kernel, pwgemm.hip) exposes HBM/L2 latency: one k-tile of prefetch, two waves per SIMD and
+// The register-staged kernel (pw_gemm_nt_kernel, pwntv1.hip) exposes HBM/L2 latency: one k-tile of prefetch, two waves per SIMD and
 // one M-tile per block leave each wave idle ~60 % of the time.  v2 fixes the structure, CDNA4-style:
 //   * global_load_lds_dwordx4 (LDS-DMA) copies tiles HBM -> LDS without touching VGPRs, so a 3-stage ring
 //     keeps two k-tiles in flight behind the one being multiplied (counted `s_waitcnt vmcnt(N)` + raw
@@ -33,8 +34,6 @@ constexpr int BM = 128;
 // Out-of-range rows are clamped to a valid row (their outputs are never stored); k-chunks past K re-read the
 // row start and are annihilated by zeroed B fragments (and zero scale/shift).
 // ------------------------------------------------------------------------------------------------
-__device__ const float4 mny_zero16 = {0.f, 0.f, 0.f, 0.f};   // DMA source for B chunks past K
-
 struct Gemm2Args {   // A / B / addend / C: float* (BF = 0) or bf16_t* (BF = 1)
     const void* A; const float* in_scale; const float* in_shift; int in_act;
     const void* B; const float* bias; const void* addend; void* C; float* stats;

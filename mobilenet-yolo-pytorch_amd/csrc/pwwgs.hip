@@ -2,7 +2,7 @@
 // project convs of the 22x22 and 11x11 bottlenecks: dW[N][K] = sum_m dY[m][:]^T act(X[m][:]) — as a barrier-free stream kernel on the
 // bf16 matrix cores.
 //
-// The LDS-DMA weight-gradient kernels (pwgemm.hip) run these shapes at 70-79 TFLOP/s, 1.7-2.8 TB/s: a 16-row chunk behind a barrier,
+// The LDS-DMA weight-gradient kernels (pwwgrad.hip) run these shapes at 70-79 TFLOP/s, 1.7-2.8 TB/s: a 16-row chunk behind a barrier,
 // fp32 MFMAs (the six-product form needs whole 16-row chunks per wave, the all-waves-share-the-tile mode hands a wave 4 rows).  Here a
 // wave owns whole 16-row chunks of its workgroup's row slice (chunks wave, wave + 4, ...), loads both operands STRAIGHT from the
 // row-major tensors in the reduction-major pattern (lane (column c, half h) -> rows 2e + h, e = 0..7, of column c: eight dword loads

@@ -8,7 +8,7 @@
 //     dW_s = dY_s^T P = ca o (dz_s^T P) + cb o (W P^T P) + cc (x) colsum(P)
 // with ca = gamma * invstd known BEFORE the sums (s1 = sum dz_s, s2 = sum dz_s * s_hat) that cb and cc need.  So the pass forms dz_s per
 // pixel, accumulates P1 = dz_s^T P (32 x 27), the patch second-moment matrix P^T P (27 x 27), colsum(P) and (s1, s2) — partial rows in
-// exactly the layout of the fused expand-unit backward (pwgemm.hip: [P1 | Gram | s1 | s2 | s3]) — and pw_bnbwd_finalize_kernel (fp64)
+// exactly the layout of the fused expand-unit backward (pwbnbwd.hip: [P1 | Gram | s1 | s2 | s3]) — and pw_bnbwd_finalize_kernel (fp64)
 // turns them into dW_s, dgamma_s, dbeta_s.  G_s is never written and S is read once: 3.4 GB.
 //
 // Workgroup = 8 channel groups (4 channels each) x 32 column slots: 30 owned columns + one halo column each side, walking down a strip of

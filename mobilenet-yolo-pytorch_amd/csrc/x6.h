@@ -1,4 +1,4 @@
-// The six-product bf16 form of an fp32 product (shared by pwgemm.hip, pwnt_kernel.h and pwwide.hip).
+// The six-product bf16 form of an fp32 product (shared by pwgemm.hip, pwnt_kernel.h, pwwgrad.hip, pwbnbwd.hip and pwwide.hip).
 #pragma once
 #include "common.h"
 

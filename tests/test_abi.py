@@ -152,7 +152,7 @@ def test_unknown_switch_warns_once_by_name(monkeypatch):
 
 # what the toolchain leaves in the dynamic table besides the C ABI, by type and prefix: the host-side kernel handle objects (one data symbol per
 # __global__ function, `D`, or per instantiation of a __global__ template, weak `V`; hipLaunchKernel takes their address), weak libstdc++
-# instantiations (std::map / std::mutex of core.hip and pwgemm.hip), and the HIP compilation-unit ids
+# instantiations (std::map / std::mutex of core.hip and pwgemm.hip, the unit of the forward / data-gradient routes), and the HIP compilation-unit ids
 _KERNEL_HANDLE = re.compile(r"_Z(N3mny)?\d+[a-z0-9_]*_kernel")
 _ALLOWED_PREFIX = {"W": ("_ZNSt", "_ZSt", "_ZNKSt"), "V": ("_ZNSt", "_ZSt", "_ZTSSt", "_ZTISt", "_ZTVSt"), "B": ("__hip_cuid_",), "D": ("__hip_cuid_",)}
 

@@ -1,4 +1,4 @@
-"""Every instantiation of the three weight-gradient tile kernels behind mny_pw_wgrad / mny_pw_wgrad_bf16 (csrc/pwgemm.hip: pw_wgrad_kernel,
+"""Every instantiation of the three weight-gradient tile kernels behind mny_pw_wgrad / mny_pw_wgrad_bf16 (csrc/pwwgrad.hip: pw_wgrad_kernel,
 pw_wgrad_dma_kernel, pw_wgrad_bf16_kernel — 113 compiled kernels) held to EQUALITY with an fp64 reference.
 
 The older direct tests launch 45 of the 113 (tests/test_wgrad_regimes_cpu.py prints which), each at one or two row counts, on seeded normal data

@@ -16,18 +16,18 @@ import pytest
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LLVM = "/opt/rocm/lib/llvm/bin"
+# counted in pwgemm.o of the last build before the split, with the code of this file: stage 1 4 fp32 + 2 bf16, finalize 1, first-generation
+# data gradient 1, second generation 3 fp32 + 3 fp32 with sums + 5 bf16
+PW_BNBWD_FUNCTIONS = 19
 
 
-@pytest.fixture(scope="module")
-def pwgemm_disassembly(tmp_path_factory):
-    import mobilenet_yolo_pytorch_amd.build as b
-    b.build()
-    obj = os.path.join(b.OBJ, "pwgemm.o")
+def _functions(obj, workdir):
+    """{function symbol: [instruction text, ...]} of the gfx950 code object inside a host object file."""
     tools = [os.path.join(LLVM, "clang-offload-bundler"), os.path.join(LLVM, "llvm-objdump"), shutil.which("objcopy")]
     if not all(t and os.path.exists(t) for t in tools):
         pytest.skip("ROCm LLVM binutils not found")
-    d = tmp_path_factory.mktemp("isa")
-    fat, co = str(d / "fat.bin"), str(d / "pwgemm.co")
+    stem = os.path.splitext(os.path.basename(obj))[0]
+    fat, co = str(workdir / (stem + ".fat.bin")), str(workdir / (stem + ".co"))
     subprocess.check_call(["objcopy", "-O", "binary", "--only-section=.hip_fatbin", obj, fat])
     subprocess.check_call([tools[0], "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--input=" + fat, "--output=" + co, "--unbundle"])
     txt = subprocess.run([tools[1], "-d", co], capture_output=True, text=True, check=True).stdout
@@ -42,9 +42,23 @@ def pwgemm_disassembly(tmp_path_factory):
     return funcs
 
 
-def test_bf16_stage2_kernels_have_no_swapped_packed_add(pwgemm_disassembly):
+@pytest.fixture(scope="module")
+def pointwise_functions(tmp_path_factory):
+    """The device functions of the five pointwise-GEMM units, per object."""
+    import mobilenet_yolo_pytorch_amd.build as b
+    b.build()
+    d = tmp_path_factory.mktemp("isa")
+    return {name: _functions(os.path.join(b.OBJ, name), d) for name in ("pwgemm.o", "pwntv1.o", "pwntred.o", "pwwgrad.o", "pwbnbwd.o")}
+
+
+@pytest.fixture(scope="module")
+def pwbnbwd_disassembly(pointwise_functions):
+    return pointwise_functions["pwbnbwd.o"]
+
+
+def test_bf16_stage2_kernels_have_no_swapped_packed_add(pwbnbwd_disassembly):
     bad_form = re.compile(r"v_pk_add_f32\b.*op_sel:\[0,1\] op_sel_hi:\[1,0\]")
-    kernels = {k: v for k, v in pwgemm_disassembly.items() if "pw_bnbwd_dgrad2_kernel" in k and "bf16_t" in k}
+    kernels = {k: v for k, v in pwbnbwd_disassembly.items() if "pw_bnbwd_dgrad2_kernel" in k and "bf16_t" in k}
     assert len(kernels) == 5, sorted(kernels)            # N = 64, 72, 96, 144, 192
     for name, body in kernels.items():
         assert len(body) > 500, name
@@ -52,3 +66,28 @@ def test_bf16_stage2_kernels_have_no_swapped_packed_add(pwgemm_disassembly):
         assert not hits, (name, hits[:3])
         # the epilogue's addend adds are there, as scalar adds behind the DPP quad transpose
         assert any("v_add_f32" in ln for ln in body) and any("row_shr" in ln or "quad_perm" in ln or "dpp" in ln.lower() for ln in body), name
+
+
+def test_every_pointwise_kernel_family_is_compiled_in_one_unit(pointwise_functions):
+    """csrc/pwgemm.hip was split by kernel family so that the families compile side by side.  A family instantiated in two units would compile
+    twice and nothing else would show it: every symbol is in one object, every family in its own, in the numbers of the tables."""
+    where = {}
+    for obj, funcs in pointwise_functions.items():
+        for sym in funcs:
+            where.setdefault(sym, []).append(obj)
+    assert not {s: o for s, o in where.items() if len(o) > 1}
+
+    def count(family):      # {object: functions of the family}; the mangled name holds <length><name>
+        out = {}
+        for sym, objs in where.items():
+            if re.search(r"\d%s(?![a-z0-9_])" % family, sym):
+                out[objs[0]] = out.get(objs[0], 0) + 1
+        return out
+
+    wg = {f: count(f) for f in ("pw_wgrad_kernel", "pw_wgrad_dma_kernel", "pw_wgrad_bf16_kernel")}
+    assert all(set(c) == {"pwwgrad.o"} for c in wg.values()), wg
+    assert sum(c["pwwgrad.o"] for c in wg.values()) == 113, wg          # 36 + 23 + 54 (tests/wgrad_regimes.py ROWS)
+    assert count("pw_bnbwd_[a-z0-9_]*") == {"pwbnbwd.o": PW_BNBWD_FUNCTIONS}
+    assert count("pw_gemm_nt_kernel") == {"pwntv1.o": 16}               # 2 storage types x 4 column tiles x 2 BK
+    assert count("pw_gemm_nt_dma_kernel") == {"pwgemm.o": 60, "pwntred.o": 43}
+    assert sum(count("reduce_parts_kernel").values()) == 1

@@ -1,4 +1,4 @@
-"""The weight-gradient tile kernels of mny_pw_wgrad / mny_pw_wgrad_bf16 (csrc/pwgemm.hip) — which of the 113 compiled instantiations a call
+"""The weight-gradient tile kernels of mny_pw_wgrad / mny_pw_wgrad_bf16 (csrc/pwwgrad.hip) — which of the 113 compiled instantiations a call
 launches and how that launch is cut — restated in pure Python:
 
     pw_wgrad_kernel<T, MODE, TI, TJ>          register-staged, T = float | bf16_t              18 tiles x 2 types = 36      template 0

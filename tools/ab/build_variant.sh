@@ -1,6 +1,6 @@
 #!/bin/bash
 # usage: bash tools/ab/build_variant.sh NAME SOURCE [extra hipcc flags...]  -> tools/ab/lib_NAME.so = the in-tree objects with csrc/SOURCE.hip
-# (pwgemm, pwntred, ...) rebuilt under the flags
+# (pwgemm, pwntred, pwntv1, pwwgrad, pwbnbwd, ...) rebuilt under the flags
 set -e
 R=$(cd "$(dirname "$0")/../.." && pwd); C=$R/mobilenet-yolo-pytorch_amd/csrc; N=$1; S=${2%.hip}; shift 2
 T=$(mktemp -d); trap 'rm -rf "$T"' EXIT

@@ -6,8 +6,10 @@
 For every *.o of either directory: the .hip_fatbin section is copied out (objcopy), the gfx950 code object unbundled
 (clang-offload-bundler) and disassembled (llvm-objdump -d), as tests/test_isa_guards_cpu.py does.  Per kernel symbol the instruction
 listing (addresses, encodings, comments and pc-relative distances stripped) and the metadata of its note record (VGPR / AGPR / SGPR counts, scratch and LDS bytes,
-kernarg size, workgroup size limit) are compared.  Prints the kernels only the parent has, only the branch has, and those whose listing or
-metadata differ; exit status 1 when a kernel was added or changed (a refactor may remove kernels, nothing else).
+kernarg size, workgroup size limit) are compared.  Functions are keyed by (object, symbol); a symbol that exactly one object holds on each side is
+matched across objects, compared like any other and counted under "moved" with both object names (LIST_MOVED=1 names each one).  Prints the
+kernels only the parent has, only the branch has, and those whose listing or metadata differ; exit status 1 when a kernel was added or
+changed (a refactor may remove or move kernels, nothing else).
 """
 import os
 import re
@@ -111,23 +113,50 @@ def demangle(names):
     return dict(zip(names, r.stdout.splitlines())) if r.returncode == 0 else {n: n for n in names}
 
 
+def pairs(parent, branch):
+    """{parent key: branch key} for two {(object, symbol): ...} surveys.  The same (object, symbol) on both sides is a pair; a symbol that
+    exactly one object holds on each side is a pair across objects (a move); a symbol several objects hold on a side stays keyed per object."""
+    holders = [{}, {}]
+    for side, keys in enumerate((parent, branch)):
+        for f, k in keys:
+            holders[side].setdefault(k, []).append(f)
+    out = {}
+    for f, k in parent:
+        if (f, k) in branch:
+            out[(f, k)] = (f, k)
+        elif len(holders[0][k]) == 1 and len(holders[1].get(k, ())) == 1:
+            out[(f, k)] = (holders[1][k][0], k)
+    return out
+
+
 def main(parent_dir, branch_dir):
     pl, pm = survey(parent_dir)
     bl, bm = survey(branch_dir)
-    removed = sorted(set(pl) - set(bl))
-    added = sorted(set(bl) - set(pl))
-    changed = sorted(k for k in set(pl) & set(bl) if pl[k] != bl[k])
-    meta_changed = sorted(k for k in set(pm) & set(bm) if pm[k] != bm[k])
-    meta_added = sorted(set(bm) - set(pm))
-    names = demangle(sorted({k[1] for k in removed + added + changed + meta_changed}))
-    print("functions: parent %d, branch %d, identical %d" % (len(pl), len(bl), len(set(pl) & set(bl)) - len(changed)))
-    print("kernel metadata records: parent %d, branch %d, identical %d" % (len(pm), len(bm), len(set(pm) & set(bm)) - len(meta_changed)))
+    lp, mp = pairs(pl, bl), pairs(pm, bm)
+    removed = sorted(set(pl) - set(lp))
+    added = sorted(set(bl) - set(lp.values()))
+    moved = sorted(k for k in lp if lp[k] != k)
+    changed = sorted(k for k in lp if pl[k] != bl[lp[k]])
+    meta_changed = sorted(k for k in mp if pm[k] != bm[mp[k]])
+    meta_added = sorted(set(bm) - set(mp.values()))
+    names = demangle(sorted({k[1] for k in removed + added + changed + meta_changed + moved}))
+    print("functions: parent %d, branch %d, identical %d (moved to another object: %d)" % (len(pl), len(bl), len(lp) - len(changed), len(moved)))
+    print("kernel metadata records: parent %d, branch %d, identical %d" % (len(pm), len(bm), len(mp) - len(meta_changed)))
     for title, keys in (("removed", removed), ("ADDED", added), ("CHANGED listing", changed), ("CHANGED metadata", meta_changed)):
         print("%s: %d" % (title, len(keys)))
         for f, k in keys:
-            print("   %-12s %s" % (f, names.get(k, k)))
+            to = (lp if title != "CHANGED metadata" else mp).get((f, k), (f, k))[0]
+            print("   %-12s %s" % (f if to == f or title == "ADDED" else f + " -> " + to, names.get(k, k)))
     for k in meta_changed:
-        print("   metadata of", names.get(k[1], k[1]), {x: (pm[k].get(x), bm[k].get(x)) for x in META_KEYS if pm[k].get(x) != bm[k].get(x)})
+        print("   metadata of", names.get(k[1], k[1]), {x: (pm[k].get(x), bm[mp[k]].get(x)) for x in META_KEYS if pm[k].get(x) != bm[mp[k]].get(x)})
+    print("moved: %d" % len(moved))      # compared like every other pair: a moved function that differs is under CHANGED too
+    routes = {}
+    for k in moved:
+        routes.setdefault((k[0], lp[k][0]), []).append(k)
+    for (src, dst), keys in sorted(routes.items()):
+        print("   %s -> %s: %d" % (src, dst, len(keys)))
+        for k in keys if os.environ.get("LIST_MOVED") else ():
+            print("      " + names.get(k[1], k[1]))
     return 1 if (added or changed or meta_changed or meta_added) else 0
 
 

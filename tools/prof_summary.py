@@ -125,7 +125,7 @@ def main():
         # the fused backward of the thin expand units: stage 1 + finalize + stage 2 (the entry point's own partial combine rides along)
         "mny_pw_bnbwd": lambda k: k.startswith("pw_bnbwd_"),
         # the fused depthwise backward (round 4: priced) and the expand + depthwise unit (exdw.hip; its backward = pass 1 + 2; the shared
-        # finalize / combine kernels of pwgemm.hip it launches are counted under mny_pw_bnbwd's name filter when that entry point also runs)
+        # finalize / combine kernels of pwbnbwd.hip / pwwgrad.hip it launches are counted under mny_pw_bnbwd's name filter when that entry point also runs)
         "mny_dw_bnbwd": lambda k: bool(re.match(r"dw_bnbwd_s1k3_kernel<.*, false>$", k)),
         "mny_dw_bnbwd_red": lambda k: bool(re.match(r"dw_bnbwd_s1k3_kernel<.*, true>$", k)),
         "mny_dw_bnbwd_s2": lambda k: k.startswith("dw_bnbwd_s2k3_kernel"),
