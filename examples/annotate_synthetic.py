@@ -3,11 +3,12 @@
 file per image — and the val_batch*_pred.jpg contact sheet YOLO trainers write — with every pixel staying on the device until
 it is a quantised coefficient.
 
-    python examples/annotate_synthetic.py [--batch 8] [--size 352] [--seg 2] [--out annotated] [--quality 75]
+    python examples/annotate_synthetic.py [--batch 8] [--size 352] [--seg 2] [--names voc|bdd|none] [--out annotated] [--quality 75]
 
 The batch is synthetic photos through BatchPrep; the weights are random, so the boxes are many and meaningless.  With --seg C the
 config gets a `seg:` section and the seg probabilities (segeval.upsample at the network size) dim channel G for class 0 and R
-for class 1, as the reference does.  Class names are not drawn; a class is a colour."""
+for class 1, as the reference does.  Every box carries "name score" (--names voc, the default; bdd: that dataset's ten names, classes
+beyond them labelled by their index; none: colours alone, as before names could be drawn)."""
 import argparse
 import os
 import sys
@@ -29,6 +30,7 @@ def main():
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--size", type=int, default=352)
     ap.add_argument("--seg", type=int, default=0, help="classes of a segmentation head (0: the VOC config, no head; at most 2)")
+    ap.add_argument("--names", choices=("voc", "bdd", "none"), default="voc", help="the class names drawn on the boxes")
     ap.add_argument("--out", default="annotated")
     ap.add_argument("--quality", type=int, default=75)
     a = ap.parse_args()
@@ -46,7 +48,8 @@ def main():
     if a.seg:
         dets = out[0]
         probs = segeval.upsample(model.seg_logits(), [(a.size, a.size)] * a.batch)     # [C,H,W] probabilities per image, on the device
-    ann = Annotator(thickness=2, score_thres=0.15)
+    names = {"voc": synthetic.VOC_NAMES, "bdd": synthetic.BDD_NAMES, "none": None}[a.names]
+    ann = Annotator(thickness=2, score_thres=0.15, names=names)
     enc = JpegEncoder(quality=a.quality, subsampling="4:2:0", device=dev)
     os.makedirs(a.out, exist_ok=True)
     buf, desc = ann.annotate(images, dets=dets, seg_probs=probs, mean=MEAN, std=STD)   # inference.py:70-103

@@ -1159,12 +1159,13 @@ int mny_jpeg_huffman_batch(const int16_t* coef, int64_t coef_elems, const mny_jp
                            const int64_t* out_off, const int64_t* out_cap, int64_t* out_len, int32_t* status,
                            int n_threads);
 
-/* ---- annotation: draw records, then source + box outlines + seg overlay into uint8 images (csrc/viz.hip) ----------------
+/* ---- annotation: draw records, then source + box outlines and labels + seg overlay into uint8 images (csrc/viz.hip) -----
  * The reference's inference product (inference.py:58-104) draws the kept boxes on the decoded image and dims the
  * drivable-area pixels; YOLO trainers write train_batch*.jpg / val_batch*_pred.jpg the same way.  Here both run on the
- * device, on what the other stages left there, and the result feeds mny_jpeg_coef_batch.  Class names are not drawn (no
- * font): class identity is by colour.  No host sync, no allocation, no atomics; deterministic; tests/viz_ref.py restates
- * both entry points in numpy.
+ * device, on what the other stages left there, and the result feeds mny_jpeg_coef_batch.  Class names and scores
+ * (inference.py:90-95) are drawn from coverage strips the caller renders once with its font (mny_viz_labels,
+ * mny_viz_compose_labels); the library holds no font.  No host sync, no allocation, no atomics; deterministic;
+ * tests/viz_ref.py and tests/vizlabel_ref.py restate the entry points in numpy.
  *
  * mny_viz_boxes: rows / seg_begin / seg_count / S / capacity as mny_nms_per_class takes them; dims (DEVICE, [S]): h and w of
  *   the image of segment s (offset is not read).  Record i belongs to row i: nothing is compacted, no count comes back; rows
@@ -1215,6 +1216,69 @@ int mny_viz_compose(const float* batch, int H, int W, const float* mean3, const 
                     const mny_image_desc* desc, const mny_viz_item* items, int N, const mny_viz_box* boxes,
                     const int32_t* seg_begin, const int32_t* seg_count, int capacity, const float* seg, int C,
                     const int32_t* seg_channel, uint8_t* dst, void* ws, void* stream);
+
+/* ---- annotation, text: "name score" on every drawn box (csrc/viz.hip) ----------------------------------------------------
+ * The strip atlas (DEVICE, the caller's, rendered once with any font): n_names + 12 coverage strips of one line height h,
+ * strip k a uint8 [h, w_k] image, row-major, at atlas + strips[2 k], with w_k = strips[2 k + 1] (strips: DEVICE, int32
+ * [n_names + 12, 2]).  Strips 0 .. n_names - 1 are the class names rendered whole (a font may kern, or reach outside a
+ * character's cell); strips n_names + 0 .. + 11 are the single characters "0123456789. " in that order.  Coverage 0 is
+ * background, 255 is ink.  Limits: h in 1..MNY_VIZ_MAX_TEXT_H, n_names in 0..MNY_VIZ_MAX_NAMES (checked); every w_k in
+ * 0..MNY_VIZ_MAX_STRIP_W and every strip inside the atlas (the caller's: the table is on the device).
+ *
+ * mny_viz_labels: rows / mode / seg_begin / seg_count / S / capacity / dims as mny_viz_boxes took them, and boxes = the
+ *   records it wrote.  Label record i sits beside box record i: nothing is compacted, no count comes back, rows outside
+ *   every segment keep what `out` held.  The label is EMPTY (48 zero bytes; n = 0) where boxes[i] is empty (t = 0: the
+ *   gate is decided once, by mny_viz_boxes), in mode 1 when label_targets is 0, and where the row's class is NaN,
+ *   negative or >= 2^24 (which no row of a drawn record is).  Otherwise:
+ *   strips: seq[0 .. n).  c = (int)cls.  c < n_names: the one strip c.  Else the decimal digits of c, most significant first,
+ *     no leading zeros (strips n_names + digit): at most 8, as c < 2^24.  In mode 0 with with_score != 0 five more follow:
+ *     with k = rint((double)(conf * cls_score) * 100.0) clamped to 0..999, where conf * cls_score is the one fp32 product of
+ *     the gate, the product by 100 is exact in fp64 and rint rounds ties to even, the strips of ' ', k / 100, '.',
+ *     k / 10 % 10, k % 10.  For a product below 9.995 these are the characters of printf("%.2f").  n is at most
+ *     MNY_VIZ_LABEL_STRIPS = 8 + 5.
+ *   size: tw = the sum of the n strip widths; lw = tw + 2 * pad with pad = 2; lh = h.
+ *   place (int32, from the box record's x0, y0 and the segment's dims.w = W): ly = y0 - lh if that is >= 0, else y0 (the
+ *     label hangs inside the box); lx = max(min(x0, W - lw), 0).
+ *   colours: bg = the box record's rgb; fg = text_rgb (HOST, 3 bytes, read during the call); filled = (filled != 0).
+ *
+ * mny_viz_compose_labels: mny_viz_compose with labels (DEVICE, beside boxes: labels[seg_begin[n] + r] belongs to
+ *   boxes[seg_begin[n] + r]), the atlas and its table.  labels == NULL: mny_viz_compose, byte for byte (atlas and strips are
+ *   not read).  labels != NULL needs boxes, atlas and strips.  Step 2 becomes, per record in order:
+ *   a. the record's outline, by the rule of mny_viz_compose;
+ *   b. its label, if n > 0: for a pixel (x, y) of the item with lx <= x < lx + lw and ly <= y < ly + lh,
+ *        under = bg[ch] if filled, else the pixel's channel as step 1, the earlier records and (a) left it;
+ *        m = coverage at text column c = x - lx - pad, row y - ly: 0 for c < 0 or c >= tw, else the byte of the strip of seq
+ *            that holds column c when the n strips are laid side by side;
+ *        tmp = m * fg[ch] + (255 - m) * under + 128;  channel = ((tmp >> 8) + tmp) >> 8
+ *      (Pillow's ImageDraw.text through an 8-bit mask: m = 0 leaves `under`, m = 255 gives fg).  For a filled label this is
+ *      ImageDraw.rectangle([lx, ly, lx + lw - 1, ly + lh - 1], fill=bg) then ImageDraw.text((lx + pad, ly), s, fill=fg),
+ *      byte for byte, when the strips compose to Pillow's rendering of s (they do for ImageFont.load_default_imagefont()).
+ *   Later records draw over earlier ones, labels included; step 3 (the seg overlay) follows all of them and dims label
+ *   pixels too.  Pixels outside the item are never written: a label clips to its image or sheet tile.  A workgroup lists a
+ *   record when its outline or its label rectangle meets the tile, and walks its list forwards. */
+#define MNY_VIZ_LABEL_STRIPS 13
+#define MNY_VIZ_MAX_TEXT_H 64
+#define MNY_VIZ_MAX_STRIP_W 1024
+#define MNY_VIZ_MAX_NAMES 4096
+typedef struct mny_viz_label {
+    int32_t lx, ly;                     /* top-left pixel of the label rectangle */
+    int32_t lw;                         /* tw + 2 * pad */
+    uint16_t seq[MNY_VIZ_LABEL_STRIPS]; /* strip indices, left to right */
+    uint8_t n;                          /* strips used; 0 = empty record */
+    uint8_t lh;
+    uint8_t filled;                     /* 1: the rectangle is filled with bg first */
+    uint8_t bg[3], fg[3];
+    uint8_t reserved;                   /* 0 */
+} mny_viz_label; /* 48 bytes */
+int mny_viz_labels(const float* rows, int mode, const int32_t* seg_begin, const int32_t* seg_count, int S, int capacity,
+                   const mny_image_desc* dims, const mny_viz_box* boxes, const int32_t* strips, int n_names, int h,
+                   int with_score, int filled, int label_targets, const uint8_t* text_rgb, mny_viz_label* out,
+                   void* stream);
+int mny_viz_compose_labels(const float* batch, int H, int W, const float* mean3, const float* std3, const uint8_t* src,
+                           const mny_image_desc* desc, const mny_viz_item* items, int N, const mny_viz_box* boxes,
+                           const int32_t* seg_begin, const int32_t* seg_count, int capacity, const float* seg, int C,
+                           const int32_t* seg_channel, uint8_t* dst, void* ws, const mny_viz_label* labels,
+                           const uint8_t* atlas, const int32_t* strips, void* stream);
 
 /* ---- bf16 STORAGE twins (BASELINE config 4: MobileNetV3-YOLO 512x512 bf16) -----------------
  * Every `mny_X_bf16` has the contract of `mny_X` above with ONE difference: the activation-sized tensors (the

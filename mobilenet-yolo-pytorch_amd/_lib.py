@@ -220,6 +220,8 @@ _SIGS["mny_det_topk"] = (c_int, [P, P, c_int, c_int, c_int, P, P, P, P, P, P])
 _SIGS["mny_viz_boxes"] = (c_int, [P, c_int, P, P, c_int, c_int, P, c_float, P, c_int, c_int, P, P])
 _SIGS["mny_viz_ws_bytes"] = (c_size_t, [c_int])
 _SIGS["mny_viz_compose"] = (c_int, [P, c_int, c_int, P, P, P, P, P, c_int, P, P, P, c_int, P, c_int, P, P, P, P])
+_SIGS["mny_viz_labels"] = (c_int, [P, c_int, P, P, c_int, c_int, P, P, P, c_int, c_int, c_int, c_int, c_int, P, P, P])
+_SIGS["mny_viz_compose_labels"] = (c_int, [P, c_int, c_int, P, P, P, P, P, c_int, P, P, P, c_int, P, c_int, P, P, P, P, P, P, P])
 EXPORTS = tuple(_SIGS)
 
 _lib = None

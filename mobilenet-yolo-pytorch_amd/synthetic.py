@@ -16,6 +16,10 @@ VOC_CONFIG = {
         "mask": [[0, 1, 2], [3, 4, 5]],
     },
 }
+# class names of the two datasets the reference trains on (data/voc_data.yaml, data/bdd100k.yaml), index = class
+VOC_NAMES = ["aeroplane", "bicycle", "bird", "boat", "bottle", "bus", "car", "cat", "chair", "cow", "diningtable", "dog", "horse", "motorbike", "person",
+             "pottedplant", "sheep", "sofa", "train", "tvmonitor"]
+BDD_NAMES = ["person", "rider", "car", "bus", "truck", "bike", "motor", "traffic light", "traffic sign", "train"]
 
 
 def images(n, h, w, seed=0):
