@@ -338,6 +338,71 @@ int mny_det_topk(const float* rows, const int32_t* seg_begin, int S, int capacit
                  void* stream);
 size_t mny_det_topk_ws_bytes(int S, int capacity);
 
+/* ---- sliced (tiled) inference of the detection path (csrc/slice.hip; SAHI's get_sliced_prediction) ----
+ * The ORIGINAL image is cut into overlapping tiles at native resolution, every tile goes through the network as an
+ * image of its own, its candidates are mapped back into the original image and appended to that image's segment
+ * (optionally with the candidates of one whole-image view, for the large objects), and ONE NMS runs over the union.
+ * Opt-in: mny_prep_batch and mny_det_append are what they were.  No host sync, no atomics on row positions, results
+ * bit-reproducible; tests/slice_ref.py restates the three stages in numpy.
+ *
+ * The tile grid (host, slicing.tile_grid(h, w, tile_h, tile_w, overlap_h, overlap_w); the rule is SAHI's get_slice_bboxes):
+ *   the ratios lie in [0, 1);  oy = (int)(overlap_h * tile_h), ox = (int)(overlap_w * tile_w), both below the tile's size
+ *   (anything else is an argument error).  Rows k = 0, 1, ...: start = k * (tile_h - oy), end = start + tile_h; row k is
+ *   (y0, y1) = (start, end) when end <= h and is shifted back to (max(0, h - tile_h), h) when end would pass h; row 0 always
+ *   exists and row k + 1 exists when row k's unshifted end lies below h.  Columns the same with w, tile_w, ox.  Windows
+ *   (x0, y0, x1, y1) in integer pixels, row-major.  Every tile of an image that is at least tile-sized has the tile's size; an
+ *   image smaller than the tile in one axis gives windows clamped to the image in that axis.  Duplicate windows are not removed.
+ *   1280 x 720, tile 416, overlap 0.2: x starts 0, 333, 666, 864 and y starts 0, 304.
+ *
+ * mny_prep_tiles: slot b of out [B,3,out_h,out_w] is what mny_prep_batch writes for a dense copy of the window
+ *   src + tiles[b].offset, h x w pixels, rows `pitch` bytes apart: Pillow's im.crop(box).resize((out_w, out_h), BILINEAR), then
+ *   ToTensor and Normalize, bit for bit.  The window is an image of its own: the tap tables are those of an h x w image, so
+ *   the taps at the window's edge clamp at the window and never read the neighbouring pixels of the source image
+ *   (Image.resize(box=) reads them and is not the model).  A window of the output's size is a copy plus the normalisation (the
+ *   coefficient rule gives a single unit tap).  Windows of different slots may overlap.
+ *   image == -1: a padding slot, written as zeros, no status.  A window outside 1..max_h x 1..max_w or with pitch < 3*w
+ *   is written as zeros and the int32 at ws+0 receives 1 + b (0 = ok), as in mny_prep_batch.  The caller keeps
+ *   offset + (h-1)*pitch + 3*w inside src.  tiles: DEVICE [B].  mean3/std3: HOST.  ws: mny_prep_tiles_ws_bytes().
+ *
+ * mny_det_append_tiles: rows are [.,7] as mny_yolo_decode writes them, slot b's at src_rows + b*src_stride*7, normalised to
+ *   the slot's window.  The result is that of processing the slots b = 0..B-1 in ascending order.  Slot b with
+ *   n = maps[b].image in 0..N-1 (any other value, -1 = padding: nothing is appended):
+ *     read the rows r < min(src_counts[b], src_stride) (none when that is <= 0), in source order;
+ *     drop a row (x1, y1, x2, y2, ...) when, with every compare strict in fp32 (a NaN coordinate is kept),
+ *       (interior & 1) && x1 < ex   or   (interior & 4) && x2 > 1.0f - ex   or
+ *       (interior & 2) && y1 < ey   or   (interior & 8) && y2 > 1.0f - ey
+ *     (the cut-object rule: a box that touches an interior tile edge belongs to an object that a neighbouring, overlapping
+ *     tile sees whole; a side of the window on the image border is never tested);
+ *     a surviving row is written with columns 0 and 2 = (float)(ax + bx * (double)v) and columns 1 and 3 =
+ *     (float)(ay + by * (double)v): one fp64 product, one fp64 sum (no contraction), one rounding; columns 4..6 are copied;
+ *     nothing is clipped to [0, 1] (mny_yolo_decode does not clip either).  ax = 0, bx = 1, interior = 0: bit-identical copies
+ *     (of every value but -0.0, which the sum turns into +0.0).
+ *     The survivors are numbered t = 0, 1, ... in source order;  room = dst_stride - counts[n] when
+ *     0 <= counts[n] <= dst_stride, else 0 (the rule of mny_det_append);  survivor t is written to
+ *     dst_rows[n*dst_stride + counts[n] + t] when t < room and to nowhere otherwise: nothing is written outside the image's
+ *     segment.  Then counts[n] += min(total, room) and dropped[n] += total - min(total, room)  (DEVICE int32 [N]; the
+ *     caller zeroes `dropped` and checks it with the counts).
+ *   The order is part of the specification (the NMS breaks score ties by row order).  One workgroup per image walks the
+ *   slots; within a slot the compaction is an ordered wave scan, as in mny_yolo_decode_ex.  maps: DEVICE [B].
+ *   B == 0 and N == 0 are valid. */
+typedef struct mny_tile_desc {
+    int64_t offset; /* bytes from src to the window's pixel (0,0) */
+    int32_t h, w;   /* window size in pixels */
+    int32_t pitch;  /* bytes between source rows (>= 3*w) */
+    int32_t image;  /* destination image of the slot's candidates; -1 = padding slot */
+} mny_tile_desc;
+typedef struct mny_tile_map {
+    double ax, bx, ay, by; /* x' = ax + bx * x : ax = x0 / W, bx = (x1 - x0) / W, formed on the host in double; y likewise */
+    float ex, ey;          /* edge margins in tile-normalised units: (float)(edge / out_w), (float)(edge / out_h) */
+    int32_t image;         /* destination image, -1 = padding slot (nothing appended) */
+    uint32_t interior;     /* bit 0 left, 1 top, 2 right, 3 bottom: that side of the window is NOT on the image border */
+} mny_tile_map;
+size_t mny_prep_tiles_ws_bytes(int B, int max_h, int max_w, int out_h, int out_w);
+int mny_prep_tiles(const uint8_t* src, const mny_tile_desc* tiles, int B, int max_h, int max_w, int out_h, int out_w,
+                   const float* mean3, const float* std3, float* out, void* ws, void* stream);
+int mny_det_append_tiles(const float* src_rows, int src_stride, const int32_t* src_counts, const mny_tile_map* maps, int B,
+                         float* dst_rows, int dst_stride, int32_t* counts, int32_t* dropped, int N, void* stream);
+
 /* ---- fused backward of a depthwise 3x3 stride-1 conv + BN + activation unit ----------------------------
  * One pass over (g, y, x) instead of bn_bwd_apply + dw_bwd_weight + dw_bwd_data (7 tensor passes -> 4): rebuilds
  * dY = ca*g*act'(scale*y+shift) + cb*y + cc in registers from the coefficients `coef` = [3][C] written by

@@ -216,6 +216,10 @@ _SIGS["mny_nms_agnostic_status_offset"] = (c_size_t, [c_int, c_int])
 _SIGS["mny_nms_agnostic_prefix_offset"] = (c_size_t, [c_int, c_int])
 _SIGS["mny_det_topk_ws_bytes"] = (c_size_t, [c_int, c_int])
 _SIGS["mny_det_topk"] = (c_int, [P, P, c_int, c_int, c_int, P, P, P, P, P, P])
+# sliced inference (csrc/slice.hip)
+_SIGS["mny_prep_tiles_ws_bytes"] = (c_size_t, [c_int] * 5)
+_SIGS["mny_prep_tiles"] = (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, P, P, P, P, P])
+_SIGS["mny_det_append_tiles"] = (c_int, [P, c_int, P, P, c_int, P, c_int, P, P, c_int, P])
 # annotation (csrc/viz.hip)
 _SIGS["mny_viz_boxes"] = (c_int, [P, c_int, P, P, c_int, c_int, P, c_float, P, c_int, c_int, P, P])
 _SIGS["mny_viz_ws_bytes"] = (c_size_t, [c_int])

@@ -17,7 +17,8 @@ BASE_FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wall", "
 EXTRA = {"detect.hip": ["-ffp-contract=off"], "evalmap.hip": ["-ffp-contract=off"], "prep.hip": ["-ffp-contract=off"],
          "augment.hip": ["-ffp-contract=off"], "augseq.hip": ["-ffp-contract=off"], "cocoeval.hip": ["-ffp-contract=off"],
          "segeval.hip": ["-ffp-contract=off"], "anchors.hip": ["-ffp-contract=off"], "augwarp.hip": ["-ffp-contract=off"],
-         "detreport.hip": ["-ffp-contract=off"], "tta.hip": ["-ffp-contract=off"], "postproc.hip": ["-ffp-contract=off"], "viz.hip": ["-ffp-contract=off"]}
+         "detreport.hip": ["-ffp-contract=off"], "tta.hip": ["-ffp-contract=off"], "postproc.hip": ["-ffp-contract=off"], "viz.hip": ["-ffp-contract=off"],
+         "slice.hip": ["-ffp-contract=off"]}
 
 
 def sources():

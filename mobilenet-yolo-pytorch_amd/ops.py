@@ -404,3 +404,41 @@ def nms_merge(rows, seg_begin, seg_count, out_idx, out_counts, prefix, out_rows,
     call("mny_nms_merge", _p(rows) if rows.numel() else None, _p(seg_begin), _p(seg_count), S, _p(out_idx), _p(out_counts), _p(prefix),
          float(thr), _p(out_rows), _st())
     return out_rows
+
+
+# ---- sliced inference (csrc/slice.hip) ---------------------------------------------------------------
+def _raw(t):
+    """a uint8 device table (mny_tile_desc / mny_tile_map records) or byte buffer"""
+    assert t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous()
+    return ctypes.c_void_p(t.data_ptr())
+
+
+def prep_tiles(src, tiles, B, max_h, max_w, out_h, out_w, mean3, std3, out=None, ws=None):
+    """src: uint8 device buffer of packed RGB HWC images; tiles: the B mny_tile_desc records as a uint8 device tensor; mean3 / std3:
+    ctypes float[3].  -> (out [B,3,out_h,out_w] fp32, ws: the int32 at ws[:4] is the status word)"""
+    B, out_h, out_w = int(B), int(out_h), int(out_w)
+    assert tiles.numel() >= 24 * B, "prep_tiles: the tile table is shorter than B records"
+    if out is None:
+        out = torch.empty(B, 3, out_h, out_w, device=src.device, dtype=torch.float32)
+    assert tuple(out.shape) == (B, 3, out_h, out_w) and out.dtype == torch.float32 and out.is_contiguous()
+    nbytes = query("mny_prep_tiles_ws_bytes", B, int(max_h), int(max_w), out_h, out_w)
+    if ws is None:
+        ws = torch.empty(nbytes, device=src.device, dtype=torch.uint8)
+    assert ws.dtype == torch.uint8 and ws.numel() >= nbytes, "prep_tiles: workspace too small"
+    call("mny_prep_tiles", _raw(src), _raw(tiles), B, int(max_h), int(max_w), out_h, out_w, mean3, std3, _p(out), _raw(ws), _st())
+    return out, ws
+
+
+def det_append_tiles(src_rows, src_counts, maps, dst_rows, counts, dropped):
+    """Append slot b's surviving rows of src_rows [B,src_stride,7], mapped through maps[b] (the B mny_tile_map records as a uint8 device
+    tensor), behind the counts[n] rows of image n = maps[b].image in dst_rows [N,dst_stride,7]; counts and dropped [N] are updated in
+    place.  -> counts"""
+    B, N = src_counts.numel(), counts.numel()
+    assert src_rows.dim() == 3 and dst_rows.dim() == 3 and src_rows.shape[2] == 7 and dst_rows.shape[2] == 7
+    assert src_rows.shape[0] == B and dst_rows.shape[0] == N and dropped.numel() == N and maps.numel() >= 48 * B
+    assert src_rows.dtype == torch.float32 and dst_rows.dtype == torch.float32
+    assert src_counts.dtype == torch.int32 and counts.dtype == torch.int32 and dropped.dtype == torch.int32
+    call("mny_det_append_tiles", _p(src_rows) if src_rows.numel() else None, src_rows.shape[1], _p(src_counts) if B else None,
+         _raw(maps) if B else None, B, _p(dst_rows) if dst_rows.numel() else None, dst_rows.shape[1], _p(counts) if N else None,
+         _p(dropped) if N else None, N, _st())
+    return counts
